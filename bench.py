@@ -8,6 +8,14 @@ timed region) through the full extraction path of Extractor.process:
   -> sample_feat_by_coord (+L2; HIP sampler)
 No host synchronisation inside a step (the keypoint count stays on the device).
 
+A plain run (``--gpus N --steps K --warmup W``) sets up, warms up, times exactly
+K steps and prints the result line.  ``--dump-outputs DIR`` also writes what the
+last timed step returned as DIR/<name>.npy; the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.  ``--full`` adds
+everything the headline figure does not need, each in a run of its own after the
+timed steps: a separate eager loop, the per-kernel rooflines, the training and
+correlation lines and the CPU baseline.
+
 Multi-GPU: one process per GPU.  ``--gpus N`` (N > 1) without a torchrun
 environment makes this process a launcher: before any GPU call it starts N
 worker processes of this same script with RANK / LOCAL_RANK / WORLD_SIZE /
@@ -104,9 +112,20 @@ def parse():
                         "r6g same box: 32 946.9, 64 963.0, but at 64 the side stream's "
                         "K=80 conv overlaps a decoder GEMM, see DESIGN 4.1m), "
                         "8 pairs for the training workloads (configs[2]: bs=8)" % EXTRACT_BATCH)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="extract: after the headline loop also measure what the headline figure "
+                        "does not need -- the separate eager loop, the per-kernel rooflines "
+                        "(--timing-steps extra steps), the corr / train_kp / train_desc lines "
+                        "and the CPU baseline.  Off by default: a plain run sets up, warms up, "
+                        "times --steps steps and prints the result line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="extract: after the timed steps write what the last timed step returned "
+                        "(descriptors, keypoint coordinates and scores up to the batch's "
+                        "keypoint count, and the per-image counts) as DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="with --full: skip the CPU baseline")
     p.add_argument("--no-secondary", action="store_true",
-                   help="extract: skip the corr / train_kp / train_desc lines timed after the "
+                   help="with --full: skip the corr / train_kp / train_desc lines timed after the "
                         "headline loop (N=1 only)")
     p.add_argument("--secondary-steps", type=int, default=10)
     p.add_argument("--graph", action="store_true",
@@ -126,6 +145,10 @@ def parse():
                         "map gradients) on synthetic maps; stub: a CPU-only step over "
                         "gloo that tests the launcher and the timing protocol")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "extract":
+        p.error("--dump-outputs is implemented for the extract workload only")
     if args.batch is None:
         args.batch = EXTRACT_BATCH if args.workload == "extract" else 8
     return args
@@ -274,7 +297,36 @@ def step(engine, ops, ws, imgs):
     idx, coord, score, counts, n_dev = ops.detect(lp, NMS_R, NUM_PTS, thr=THR,
                                                   thr_mod="abs", ws=ws, sync=False)
     desc = ops.sample_desc_nhwc(out["_local_map_nhwc"], coord, c=128, n_valid=n_dev)
-    return desc, coord, score
+    return desc, coord, score, counts, n_dev
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: what one step returned to its caller, as path/<name>.npy
+    (float32; the integer counts as float64).  The buffers are full-capacity
+    (sync=False), so they are cut at the batch's keypoint count n, as
+    ops.detect(sync=True) hands them out: desc [B,n,128], coord [B,n,2],
+    score [B,n,1], counts [B].  At most DUMP_LIMIT_BYTES in all: an array over
+    its share is written as a fixed seeded sample of its elements (in index
+    order), so two runs with the same arguments write the same elements."""
+    desc, coord, score, counts, n_dev = out
+    n = int(n_dev.item())
+    arrays = {"desc": desc[:, :n], "coord": coord[:, :n], "score": score[:, :n],
+              "counts": counts}
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if v.dtype.kind == "f" else np.float64)
+              for k, v in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        share = DUMP_LIMIT_BYTES // len(arrays)
+        for k, a in arrays.items():
+            if a.nbytes > share:
+                keep = np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False)
+                arrays[k] = a.reshape(-1)[np.sort(keep)]
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def host_cpu_info():
@@ -349,18 +401,23 @@ def main():
     engine = build_engine(world, rank, dev)
     ws = ops.DetectWorkspace()
     imgs = make_images(rank, args.batch, dev)
+    last = {}   # what the latest step returned (--dump-outputs)
+
+    def run():
+        last["out"] = step(engine, ops, ws, imgs)
     for _ in range(args.warmup):
-        step(engine, ops, ws, imgs)
+        run()
     # --graph: the step as ONE hipGraph (torch.cuda.CUDAGraph over the engine's
     # stream; the side stream joins the capture through the engine's fork/join
     # events): every replay launches every kernel of the step again on the
     # same resident inputs -- no work is cached -- without the ~150 host
     # launches.  Measured no faster (the GPU, not the host, paces the step), so
-    # the default is eager; the eager rate is always reported.
+    # the default is eager; --full times a separate eager loop first, so the
+    # eager rate is reported next to a --graph headline too.
     eager_steps = max(1, min(args.steps, 20))
-    el_eager = timed_loop(world, eager_steps, lambda: step(engine, ops, ws, imgs),
-                          torch.cuda.synchronize)
-    run = lambda: step(engine, ops, ws, imgs)
+    el_eager = None
+    if args.full:
+        el_eager = timed_loop(world, eager_steps, run, torch.cuda.synchronize)
     launch = "eager"
     if args.graph:
         graph = torch.cuda.CUDAGraph()
@@ -371,7 +428,7 @@ def main():
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         with torch.cuda.graph(graph):
-            step(engine, ops, ws, imgs)
+            last["out"] = step(engine, ops, ws, imgs)   # every replay refills these tensors
         graph.replay()
         torch.cuda.synchronize()
         run = graph.replay
@@ -379,6 +436,41 @@ def main():
     el = timed_loop(world, args.steps, run, torch.cuda.synchronize)
     images = world * args.steps * args.batch
     value = images / el
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["out"])
+    if el_eager is not None:
+        eager_value = round(world * eager_steps * args.batch / el_eager, 3)
+    else:   # an eager headline loop is the eager rate
+        eager_value = None if args.graph else round(value, 3)
+    head = {
+        "metric": "images/sec extract (640x480, 2048 kp)",
+        "value": round(value, 3),
+        "unit": "images/s",
+        "n_gpus": world,
+        "ranks_seen": ranks_seen(),
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(el / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "fp32",
+        "launch": launch,
+        "eager_value": eager_value,
+        "data": "synthetic (seeded uint8 480x640 images, ImageNet-normalised; seeded "
+                "random-init weights of the ResUNet-resnet50 + KeypointDet architecture)",
+        "config": {"workload": "HPatches-style extraction 640x480 (configs[1]): "
+                               "PoSFeat.extract + generate_kpts_single(r=1, thr=0.9 abs, "
+                               "2048) + sample_feat_by_coord",
+                   "global_batch": args.batch * world, "image": [H, W],
+                   "num_pts": NUM_PTS, "parallelism": "dp%d (image-sharded)" % world},
+    }
+    if not args.full:   # the plain run: the headline figure and nothing else
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- roofline of the dominant kernel, HIP events on the engine's stream
     # around each launch, averaged over a few extra steps
@@ -454,28 +546,8 @@ def main():
                                      round(gfl / (hb_ms * 1e-3) / 1e12 / arith["method_peak"], 4)})
 
     if rank == 0:
-        rec = {
-            "metric": "images/sec extract (640x480, 2048 kp)",
-            "value": round(value, 3),
-            "unit": "images/s",
-            "n_gpus": world,
-            "ranks_seen": ranks_seen(),
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(el / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "fp32",
-            "launch": launch,
-            "eager_value": round(world * eager_steps * args.batch / el_eager, 3),
-            "data": "synthetic (seeded uint8 480x640 images, ImageNet-normalised; seeded "
-                    "random-init weights of the ResUNet-resnet50 + KeypointDet architecture)",
-            "config": {"workload": "HPatches-style extraction 640x480 (configs[1]): "
-                                   "PoSFeat.extract + generate_kpts_single(r=1, thr=0.9 abs, "
-                                   "2048) + sample_feat_by_coord",
-                       "global_batch": args.batch * world, "image": [H, W],
-                       "num_pts": NUM_PTS, "parallelism": "dp%d (image-sharded)" % world},
+        rec = dict(head)
+        rec.update({
             "roofline": {"kernel": kdesc, "label": dom,
                          "bound": "mfma", "achieved": round(achieved, 3),
                          "peak": arith["method_peak"], "unit": "TFLOP/s",
@@ -509,7 +581,7 @@ def main():
                                    "image branch) overlaps them; frac = executed fp32-equivalent "
                                    "rate / the ceiling of the arithmetic the convs run (bf16x6: "
                                    "2500 / 6 TF)"},
-        }
+        })
     if world == 1 and not args.no_secondary:
         # the two training configs' steps and their correlation losses, timed by
         # the same protocol in this process after the headline loop, so the

@@ -152,6 +152,36 @@ def test_bench_launcher_spawns_world2():
     assert rec["value"] > 0
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the step's buffers cut at the batch's keypoint
+    count, float32 (the integer counts float64), one .npy per array; over the
+    size limit an array becomes a fixed sample, the same elements every time."""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    b, cap, n = 2, 16, 11
+    desc, coord, score = (torch.rand(b, cap, c, generator=g) for c in (128, 2, 1))
+    counts = torch.tensor([11, 7], dtype=torch.int32)
+    out = (desc, coord, score, counts, torch.tensor([n], dtype=torch.int32))
+    bench.dump_outputs(str(tmp_path / "a"), out)
+    got = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["coord", "counts", "desc", "score"]
+    np.testing.assert_array_equal(got["desc"], desc[:, :n].numpy())
+    np.testing.assert_array_equal(got["coord"], coord[:, :n].numpy())
+    np.testing.assert_array_equal(got["score"], score[:, :n].numpy())
+    np.testing.assert_array_equal(got["counts"], [11.0, 7.0])
+    assert got["desc"].dtype == np.float32 and got["counts"].dtype == np.float64
+    # a limit below desc's size: desc is sampled, identically in both runs
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), out)
+    s1, s2 = np.load(str(tmp_path / "b" / "desc.npy")), np.load(str(tmp_path / "c" / "desc.npy"))
+    np.testing.assert_array_equal(s1, s2)
+    assert s1.ndim == 1 and s1.nbytes <= 1024 and np.isin(s1, got["desc"]).all()
+    total = sum(os.path.getsize(str(tmp_path / "b" / f)) - 128 for f in os.listdir(tmp_path / "b"))
+    assert total <= 4096
+    np.testing.assert_array_equal(np.load(str(tmp_path / "b" / "coord.npy")), got["coord"])
+
+
 def test_h5_export_layout(tmp_path, monkeypatch):
     """save_h5 writes the reference's layout (managers/extractor.py:273-314):
     <desc_root>h5/<seq>/{keypoints,descriptors,scores,scales}.h5 datasets named

@@ -13,7 +13,7 @@ export PYTHONUNBUFFERED=1
 $chk 900 $o/gpu_tests.log python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread
 POSFEAT_HIP_LIB=$PWD/posfeat_amd/libposfeat_hip_ab.so $chk 600 $o/gpu_tests_ab.log python -u -m pytest tests/test_gpu_correlation.py tests/test_gpu_train_tap.py -m gpu -x -q -rs --timeout 300 --timeout-method thread
 $chk 200 $o/smoke.log python -c "import __graft_entry__ as g; g.smoke()"
-$chk 400 $o/bench.log python bench.py
+$chk 400 $o/bench.log python bench.py --full
 grep "^{" $o/bench.log > $o/bench.json || true
 [ "$2" = quick ] && exit 0
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
