@@ -613,6 +613,61 @@ size_t posfeat_match_workspace(int n1, int n2);
 int posfeat_match(const float *d1, int n1, const float *d2, int n2, int dim, int mode, float ratio,
                   int32_t *matches, int32_t *count, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- batched pair-list matching and the HPatches reprojection check -------
+ * posfeat_match over a whole pair list in four launches (one top-2 launch
+ * over a flat tile list covering both sides of every pair, one merge, one
+ * select with a workgroup per pair, after one plan upload), for the loops of
+ * evaluations/hpatches/evaluation.py:49-67 (image 1 against images 2..6 of
+ * every sequence) and evaluations/aachen/reconstruct_pipeline.py
+ * match_features (one matcher call per listed pair).
+ *
+ * desc [N][dim] is one pool of descriptors (dim == 128, 16-B aligned); set s
+ * is its rows [set_off[s], set_off[s+1]).  set_off (nsets + 1 entries) and
+ * pairs (npairs x (s1, s2)) are HOST arrays; pairs may share sets on either
+ * side.  Pair p writes its matches at row moff[p] = sum_{q<p} n1(q) of
+ * matches [sum n1][2], ascending in the first index, with the set-local
+ * indices, mode, ratio arithmetic and tie rule of posfeat_match (the
+ * similarity bits do not depend on how the plan splits the rows, so the
+ * output equals posfeat_match's on that pair alone); counts[p] (device) = rows
+ * written; a pair with an empty side gives counts[p] = 0.
+ * Returns, before any device work: POSFEAT_E_INVALID for a null pointer, a
+ * set index out of range, a negative or decreasing set_off, or sum n1 past
+ * INT32_MAX; POSFEAT_E_UNSUPPORTED for dim != 128 or mode outside 0..2;
+ * POSFEAT_E_WORKSPACE for ws_bytes below posfeat_match_pairs_workspace (0 for
+ * an invalid table).  ws must be 256-B aligned.
+ * Stream-ordered, never waits for its own kernels; NOT graph-capturable: the
+ * call copies its plan (side and tile tables) from pageable host memory into
+ * ws, a copy the runtime may carry out before it returns.
+ * posfeat_match_pairs_splits (host only) reports the plan: nsplit[2p] and
+ * nsplit[2p+1] = the number of row ranges the d2 rows (side "rows of sim")
+ * and the d1 rows (side "columns") of pair p are cut into; 0 for a pair with
+ * an empty side. */
+size_t posfeat_match_pairs_workspace(const int32_t *set_off, int nsets, const int32_t *pairs,
+                                     int npairs);
+int posfeat_match_pairs_splits(const int32_t *set_off, int nsets, const int32_t *pairs, int npairs,
+                               int32_t *nsplit);
+int posfeat_match_pairs(const float *desc, const int32_t *set_off, int nsets, const int32_t *pairs,
+                        int npairs, int dim, int mode, float ratio, int32_t *matches,
+                        int32_t *counts, void *ws, size_t ws_bytes, void *stream);
+
+/* The homography check of evaluations/hpatches/evaluation.py:69-90 on the
+ * matches posfeat_match_pairs left: kp [N][2] fp32 keypoints (x, y) with the
+ * row numbering of desc, set_off / pairs the same host tables, H [npairs][9]
+ * fp64 row-major homographies (device).  Per match (a, b) of pair p, in fp64:
+ * project (x_a, y_a, 1) by H[p], divide by the third component, take the
+ * Euclidean distance to (x_b, y_b); hist[p][t-1] (int32 [npairs][nthr],
+ * device) = the number of matches with dist <= t for t = 1..nthr
+ * (1 <= nthr <= 32, else POSFEAT_E_INVALID).  NaN / inf distances count
+ * nowhere; a pair without matches gives zeros.  ws: 256-B aligned,
+ * posfeat_reproj_hist_workspace(npairs) bytes (the per-pair offsets, copied
+ * from host memory: stream-ordered, no host synchronisation, not
+ * graph-capturable). */
+size_t posfeat_reproj_hist_workspace(int npairs);
+int posfeat_reproj_hist(const float *kp, const int32_t *set_off, int nsets, const int32_t *pairs,
+                        int npairs, const int32_t *matches, const int32_t *counts,
+                        const double *H, int nthr, int32_t *hist, void *ws, size_t ws_bytes,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif

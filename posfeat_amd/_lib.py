@@ -202,6 +202,14 @@ SIGNATURES = {
                                        c_void_p, c_size_t, c_void_p]),
     "posfeat_match": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, ctypes.c_float,
                               c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "posfeat_match_pairs_workspace": (c_size_t, [c_void_p, c_int, c_void_p, c_int]),
+    "posfeat_match_pairs_splits": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "posfeat_match_pairs": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
+                                    ctypes.c_float, c_void_p, c_void_p, c_void_p, c_size_t,
+                                    c_void_p]),
+    "posfeat_reproj_hist_workspace": (c_size_t, [c_int]),
+    "posfeat_reproj_hist": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 
