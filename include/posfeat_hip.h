@@ -113,6 +113,22 @@ int posfeat_conv2d_nhwc_planes(const posfeat_conv_desc *d, const float *x, const
                                const unsigned short *wb, long long wplane, const float *bias,
                                const float *res, float *y, void *ws, size_t ws_bytes, int tile,
                                void *stream);
+/* The launch plan posfeat_conv2d_nhwc_ws (wplanes = 0) or
+ * posfeat_conv2d_nhwc_planes (wplanes = 1) would take for d with every
+ * workspace it asks for and the given tile argument, for the calling thread
+ * at the current conv precision.  Host only: needs no device, launches
+ * nothing.  POSFEAT_E_INVALID for a descriptor the convs reject. */
+typedef struct {
+  int tile;           /* tile id launched (after any substitution)         */
+  int variant;        /* kernel instantiation (conv_plan.h ConvVariant)    */
+  const char *kernel; /* its name, a static string                         */
+  int bm, bn;         /* output rows / columns per workgroup               */
+  int ksplit;         /* split-K factor (1: none)                          */
+  int grid, block;    /* workgroups (ksplit included), threads per group   */
+  int arith;          /* 0: fp32 MFMA products, 1: bf16x6                  */
+} posfeat_conv_plan_info;
+int posfeat_conv_plan_query(const posfeat_conv_desc *d, int wplanes, int tile,
+                            posfeat_conv_plan_info *out);
 /* A torchvision Bottleneck's conv3 + downsample branch as ONE GEMM (the
  * reference's ResUNet encoder, networks/DescNet.py:29-35, through torchvision's
  * Bottleneck: relu(bn3(conv3(t)) + bn_ds(conv_ds(x))) with both BatchNorms

@@ -28,6 +28,12 @@ class ConvDesc(ctypes.Structure):
                                      "stride", "pad", "y_cstride", "res_cstride", "act")]
 
 
+class ConvPlanInfo(ctypes.Structure):
+    _fields_ = [("tile", c_int), ("variant", c_int), ("kernel", ctypes.c_char_p), ("bm", c_int),
+                ("bn", c_int), ("ksplit", c_int), ("grid", c_int), ("block", c_int),
+                ("arith", c_int)]
+
+
 class ExtractOut(ctypes.Structure):
     _fields_ = [("local_map", c_void_p), ("global_map", c_void_p), ("global_feat", c_void_p),
                 ("local_point", c_void_p), ("local_map_small", c_void_p),
@@ -55,6 +61,8 @@ SIGNATURES = {
     "posfeat_conv2d_nhwc_planes": (c_int, [ctypes.POINTER(ConvDesc), c_void_p, c_void_p, c_void_p,
                                            ctypes.c_longlong, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_size_t, c_int, c_void_p]),
+    "posfeat_conv_plan_query": (c_int, [ctypes.POINTER(ConvDesc), c_int, c_int,
+                                        ctypes.POINTER(ConvPlanInfo)]),
     "posfeat_conv1x1_dual": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
                                      c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                      c_void_p, c_int, c_void_p]),
@@ -303,6 +311,20 @@ def bbtrain_table():
         layers.append((name.value.decode(), ci.value, co.value, k.value, s.value, bool(hb.value),
                        tuple(int(o) for o in offs)))
     return layers, int(L.posfeat_bbtrain_param_floats()), int(L.posfeat_bbtrain_stat_floats())
+
+
+def conv_plan_query(n, h, w, cin, cout, k, stride, pad, wplanes=False, tile=-1, xcs=None):
+    """The launch plan of a conv (host only, no device needed): a dict of the
+    posfeat_conv_plan_info fields, or None for a descriptor the convs reject."""
+    cin = (cin + 3) // 4 * 4
+    d = ConvDesc(n=n, h=h, w=w, cin=cin, x_cstride=xcs or cin, cout=cout, kh=k, kw=k,
+                 stride=stride, pad=pad, y_cstride=cout, res_cstride=0, act=0)
+    info = ConvPlanInfo()
+    if lib().posfeat_conv_plan_query(ctypes.byref(d), int(wplanes), tile, ctypes.byref(info)) != 0:
+        return None
+    out = {f: getattr(info, f) for f, _ in ConvPlanInfo._fields_}
+    out["kernel"] = out["kernel"].decode()
+    return out
 
 
 def model_specs():

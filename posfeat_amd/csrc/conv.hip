@@ -20,6 +20,7 @@
 // of 8 contracts k-pair {j, 4+j} -- the same permutation on A and B, so the
 // product is exact f32 fmaf chains in a fixed (deterministic) order.
 #include "common.h"
+#include "conv_plan.h"
 #include "fmap.h"
 
 // Product arithmetic of the row-tile convs / GEMMs (posfeat_set_conv_precision):
@@ -2640,561 +2641,99 @@ __global__ void conv_splitk_reduce(const float* __restrict__ part, int ks, int M
 }
 
 // ---------------------------------------------------------------------------
-// Launch planning: one Plan decides kernel, tile and split for a conv so the
-// launch, the split-K workspace and the stats reduction agree on the tiling.
-enum ConvKern { KERN_STAGED = 0, KERN_GLDS = 1, KERN_HALO = 2 };
-enum ConvTile {
-  TILE_128x128 = 0, TILE_128x64 = 1, TILE_64x64 = 2, TILE_256x128 = 3,  // contiguous rows
-  TILE_H8x128 = 10, TILE_H8x64 = 11, TILE_H16x128 = 12,                 // 8/16 x 16 patches
-  TILE_BF6_128x128 = 20, TILE_BF6_128x256 = 21, TILE_BF6_64x128 = 22,   // rows, bf16x6 products
-  TILE_BF6_128x64 = 23, TILE_BF6B_128x128 = 24, TILE_BF6B_128x64 = 25,  // + pre-split weights
-  TILE_BF6R_128x128 = 26, TILE_BF6R_128x64 = 27,  // + A straight to registers
-  TILE_BF6B_256x128 = 28,  // pre-split weights, 8 waves stacked along M (one 135-KB block per CU)
-  TILE_BF6X_128x128 = 29, TILE_BF6X_128x64 = 30,  // dense, 16x16x32 MFMAs (conv_bf6x_kernel)
-  TILE_BF6X_256x128 = 31,
-  TILE_BF6X_128x192 = 32,  // N % 192 == 0 (head.conv1's Winograd GEMMs, the tap GEMM): A read once per 192 columns
-  TILE_BF6X_128x256 = 33,  // N % 256 == 0 batched GEMMs (A/B POSFEAT_BF6X_N256: A read once per 256 columns)
-  TILE_BF6X_192x128 = 34,  // dense: six waves stacked along M, the B tile's L2 -> CU bytes per output 2/3
-  TILE_BF6X_256x64 = 35    // dense / G4 (the stem), 64 columns: RB = 4, half the B bytes per output
-};
+// Launch planning is conv_plan.h: a pure function (ConvShape, ConvMode) ->
+// Plan.  Here: the ambient state captured into a ConvMode, once per call, and
+// the one dispatch on Plan::variant.
+static_assert(BK == CONV_BK, "conv_plan.h plans for the kernels' K chunk");
 
-// POSFEAT_BF6=1: every conv the row-tile DMA kernel serves (1x1, strided, the
-// batched Winograd / tap GEMMs) runs its products as bf16x6 (fp32-exact,
-// see split3); 3x3 stride-1 convs keep the fp32 halo kernel.  The candidate
-// set of a conv is then either all-bf16x6 or all-fp32, so the autotuner's
-// choice never changes results.
-bool bf6_on() { return pf_conv_precision() >= 1; }
-// the 3x3 stride-1 halo kernel in bf16x6 too (POSFEAT_BF6_HALO=0: fp32 MFMA);
 // PfHaloFp32Scope keeps the calling thread's launches on fp32 halo tiles (the
 // train-mode backbone, whose fp64-pinned gradient fixtures were validated on
 // them, bbtrain.hip)
 thread_local int tl_halo_fp32 = 0;
 thread_local int tl_dense32 = 0;  // PfDense32Scope
 thread_local int tl_stem32 = 0;   // PfHaloFp32Scope(false)
-bool halo_bf6_on() {
-  static const bool off = [] {
-    const char* e = pf_ab_getenv("POSFEAT_BF6_HALO");
-    return e && e[0] == '0';
+
+// The switches for A/B timing (ConvMode documents each; the defaults are the
+// tuned choice), read once per process.  POSFEAT_CONV_TILE, which the tile
+// tests use, is read by the shipped library too.
+const ConvMode& conv_switches() {
+  static const ConvMode sw = [] {
+    ConvMode m;
+    auto is = [](const char* name, char c) {
+      const char* e = pf_ab_getenv(name);
+      return e && e[0] == c;
+    };
+    m.bf6_halo = !is("POSFEAT_BF6_HALO", '0');
+    if (const char* e = pf_ab_getenv("POSFEAT_BF6D")) {
+      // same box, r6q, two pairs each: D = 2 973.1, 3 968.4, 4 966.3 img/s;
+      // bit-identical (test_gpu_bf6r.py)
+      const int v = atoi(e);
+      m.bf6d = v >= 2 && v <= 4 ? v : 0;
+    }
+    m.bf6x = !is("POSFEAT_BF6X", '0');
+    m.bf6_stem = !is("POSFEAT_BF6_STEM", '0');
+    if (const char* e = pf_ab_getenv("POSFEAT_CONV_MAXSPLIT")) m.maxsplit = atoi(e);
+    if (is("POSFEAT_CONV_KERNEL", 's')) m.kmax = KERN_STAGED;
+    if (is("POSFEAT_CONV_KERNEL", 'g')) m.kmax = KERN_GLDS;
+    if (const char* e = getenv("POSFEAT_CONV_TILE")) m.tile = atoi(e);
+    m.bm192 = is("POSFEAT_BF6X_BM192", '1');
+    m.rb4n64 = is("POSFEAT_BF6X_RB4N64", '1');
+    m.gemm_b256 = is("POSFEAT_GEMM_B256", '1');
+    m.rb4 = is("POSFEAT_BF6X_RB4", '1');
+    m.n256 = is("POSFEAT_BF6X_N256", '1');
+    // (off: the fp64 fixture step's errors unchanged, same-box train_desc
+    // +0.5..2 % over four pairs but the per-label breakdown flat)
+    m.train_wino_bf6x = is("POSFEAT_TRAIN_WINO_BF6X", '1');
+    // (r16zz4, B = 32, two runs: 0.628 -> 0.484, 0.087 -> 0.076, 0.078 ->
+    // 0.070 ms for K = 192, 128, 256; bit-identical)
+    if (const char* e = pf_ab_getenv("POSFEAT_WSB")) m.wsb = atoi(e);
+    return m;
   }();
-  return bf6_on() && !off && tl_halo_fp32 == 0;
-}
-// Dense pre-split tiles (TILE_BF6B_*) and the register-A candidates
-// (TILE_BF6R_*: any conv, masked taps included) run conv_bf6d_kernel with A
-// prefetched POSFEAT_BF6D = 2..4 chunks ahead in registers (default 2; 0: the
-// LDS-staged conv_bf6b_kernel).  The 8-wave TILE_BF6B_256x128 caps D at 3 (its
-// register budget at two waves per SIMD): D = 4 runs D = 3 there.  (Round 2's
-// register-A twin with a one-chunk prefetch, conv_bf6r_kernel, and the
-// persistent conv_bf6p_kernel lost their A/Bs and are no longer built.)  Same box,
-// r6k: 945.6 -> 970 img/s (D = 3), decoder Winograd GEMMs -4..-7 %, tap GEMM
-// -9 %; r6q, two pairs each: D = 2 973.1, 3 968.4, 4 966.3 img/s;
-// bit-identical (test_gpu_bf6r.py)
-int bf6d_depth() {
-  static const int d = [] {
-    const char* e = pf_ab_getenv("POSFEAT_BF6D");
-    const int v = e ? atoi(e) : 2;
-    return v >= 2 && v <= 4 ? v : 0;
-  }();
-  return d;
+  return sw;
 }
 
-// Dense pre-split GEMMs / 1x1 convs (no padding, stride 1) run the 16x16x32
-// conv_bf6x_kernel (POSFEAT_BF6X=0: the 32x32x16 bf6d tiles, A/B).  Their
-// candidate set is then the two BF6X tiles only, so the autotuner's choice
-// never changes results (the 16x16x32 sums are not bit-identical to the
-// 32x32x16 tiles').  The train-mode backbone (PfHaloFp32Scope) keeps the
-// 32x32x16 tiles: its one-step gradient against fp64 on the 2 x 128 x 160
-// fixture case (BatchNorm over 160 pixels in layer3) moved from a worst
-// per-tensor error of 0.014 (both 32x32 arithmetics) to 0.117 with the
-// 16x16x32 sums (tools/bb_step_err.py), while every conv
-// and the extraction model stay within the fp32 bounds (test_gpu_bf6x.py).
-bool bf6x_on() {
-  static const bool off = [] {
-    const char* e = pf_ab_getenv("POSFEAT_BF6X");
-    return e && e[0] == '0';
-  }();
-  return bf6_on() && !off && tl_halo_fp32 == 0 && tl_dense32 == 0;
-}
-// 1x1, no padding, any stride (a strided 1x1 conv is a GEMM over the
-// subsampled pixel rows: conv_bf6x_kernel maps each row to its input pixel)
-bool dense_gemm(const ConvArgs& a) {
-  return a.KH == 1 && a.KW == 1 && a.pad == 0 && a.wb && !a.xb;
-}
-// Cin % 32 == 0 convs with taps or padding (3x3 stride 1 / 2): the bf6x tile
-// gathers each lane's rows per (slab, tap) chunk (conv_bf6x_kernel GT)
-bool gt_gemm(const ConvArgs& a) {
-  return a.Cin % BK == 0 && !(a.KH == 1 && a.KW == 1 && a.pad == 0) && a.KH * a.KW <= 32 &&
-         a.wb && !a.xb;
-}
-// 4-channel input (NHWC4: the 7x7 stem), K order (kh, kw, c4): the bf6x tile
-// gathers each lane's two taps per chunk (conv_bf6x_kernel G4)
-bool g4_gemm(const ConvArgs& a) {
-  return a.Cin == 4 && a.xcs == 4 && a.KW >= 5 && a.KW <= 8 && a.wb && !a.xb &&
-         a.Kpad == (a.KH * a.KW * 4 + BK - 1) / BK * BK;
+// the mode of the calling thread, now
+ConvMode conv_mode() {
+  ConvMode m = conv_switches();
+  m.precision = pf_conv_precision();
+  m.halo_fp32 = tl_halo_fp32 != 0;
+  m.dense32 = tl_dense32 != 0;
+  m.stem32 = tl_stem32 != 0;
+  return m;
 }
 
-struct Plan {
-  int kern, tile, bm, bn, ppi;  // ppi: patches per image (halo), 0 = contiguous rows
-  long long tiles_m;
-  int ksplit;
-};
-
-// Environment switches for A/B timing only (defaults are the tuned choice):
-// POSFEAT_CONV_KERNEL=staged|glds|halo caps the kernel family, POSFEAT_CONV_TILE
-// forces a tile id where legal.
-struct ConvEnv {
-  int kmax = KERN_HALO, tile = -1, maxsplit = 4;
-  ConvEnv() {
-    if (const char* e = pf_ab_getenv("POSFEAT_CONV_MAXSPLIT")) maxsplit = atoi(e);
-    if (const char* e = pf_ab_getenv("POSFEAT_CONV_KERNEL")) {
-      if (e[0] == 's') kmax = KERN_STAGED;
-      else if (e[0] == 'g') kmax = KERN_GLDS;
-    }
-    if (const char* e = getenv("POSFEAT_CONV_TILE")) tile = atoi(e);
-  }
-};
-const ConvEnv& conv_env() {
-  static const ConvEnv e;
-  return e;
-}
-
-// Split-K factor: only for deep K (>= 64 chunks) where the tile count leaves
-// the last round of resident workgroups badly underfilled.
-int choose_ksplit(long long tiles, int nch, double slots) {
-  // (splitting underfilled grids' shorter K too was measured no faster, r3v)
-  if (nch < 64) return 1;
-  int best = 1;
-  double best_eff = 0.0;
-  for (int ks = 1; ks <= conv_env().maxsplit; ++ks) {
-    if (nch / ks < 32) break;
-    const double r = tiles * ks / slots;
-    const double eff = r / ceil(r) * (ks == 1 ? 1.0 : 0.97);  // ~3% for the reduce pass
-    // split only for a clear gain (A/B at 480x640: decoder layers gain nothing)
-    if (eff > best_eff * 1.08) {
-      best_eff = eff;
-      best = ks;
-    }
-  }
-  return best;
-}
-
-// Geometry of one tile id for this conv (ksplit = 1); kern = -1 if illegal.
-Plan plan_for_tile(const ConvArgs& a, int tile) {
-  Plan p{};
-  p.kern = -1;
-  p.tile = tile;
-  p.ksplit = 1;
-  const bool cin32 = a.Cin % BK == 0;
-  const bool halo_ok = cin32 && conv_env().kmax >= KERN_HALO && a.stride == 1 && a.KH == 3 &&
-                       a.KW == 3 && a.OW >= 16 && a.OH >= 8 && a.Cout % 64 == 0;
-  const bool glds_ok = cin32 && conv_env().kmax >= KERN_GLDS && a.KH * a.KW <= 32;
-  // bf16x6 mode: halo-eligible convs keep fp32 halo tiles only, the rest
-  // bf16x6 row tiles only
-  if (bf6_on() && glds_ok) {
-    // pre-split convs on the bf6x tiles (dense GEMMs, slab x tap gathers):
-    // the 16x16x32 tiles only, and only they
-    const bool x_tile = tile >= TILE_BF6X_128x128 && tile <= TILE_BF6X_256x64;
-    if (bf6x_on() && (dense_gemm(a) || gt_gemm(a))) {
-      if (!x_tile) return p;
-    } else {
-      if (x_tile) return p;
-      const bool bf6_tile = tile >= TILE_BF6_128x128 && tile <= TILE_BF6B_256x128;
-      if (halo_ok ? bf6_tile || tile < TILE_H8x128 : !bf6_tile) return p;
-    }
-  }
-  switch (tile) {
-    case TILE_BF6X_128x128:
-    case TILE_BF6X_128x64:
-    case TILE_BF6X_256x128:
-    case TILE_BF6X_128x192:
-    case TILE_BF6X_128x256:
-    case TILE_BF6X_192x128:
-    case TILE_BF6X_256x64:
-      if (!bf6x_on() || !((glds_ok && (dense_gemm(a) || gt_gemm(a))) || g4_gemm(a))) return p;
-      if (g4_gemm(a) && tile != TILE_BF6X_128x64 && tile != TILE_BF6X_256x64) return p;
-      if (tile == TILE_BF6X_128x192 && (!dense_gemm(a) || a.Cout % 192)) return p;
-      if (tile == TILE_BF6X_128x256 && (!dense_gemm(a) || a.Cout % 256)) return p;
-      if (tile == TILE_BF6X_192x128 && !dense_gemm(a) && !a.x2) return p;
-      if (tile == TILE_BF6X_256x64 && !dense_gemm(a) && !g4_gemm(a)) return p;
-      p.kern = KERN_GLDS;
-      p.bm = tile == TILE_BF6X_256x128 || tile == TILE_BF6X_256x64 ? 256
-             : tile == TILE_BF6X_192x128                          ? 192
-                                                                  : 128;
-      p.bn = tile == TILE_BF6X_128x64 || tile == TILE_BF6X_256x64 ? 64
-             : tile == TILE_BF6X_128x192 ? 192
-             : tile == TILE_BF6X_128x256 ? 256
-                                         : 128;
-      p.ppi = 0;
-      p.tiles_m = (a.M + p.bm - 1) / p.bm;
-      return p;
-    case TILE_BF6B_256x128:
-      if (!glds_ok || !bf6_on() || !a.wb || a.Cout <= 64) return p;
-      p.kern = KERN_GLDS;
-      p.bm = 256;
-      p.bn = 128;
-      p.ppi = 0;
-      p.tiles_m = (a.M + p.bm - 1) / p.bm;
-      return p;
-    case TILE_BF6B_128x128:
-    case TILE_BF6B_128x64:
-    case TILE_BF6R_128x128:
-    case TILE_BF6R_128x64:
-      if (!glds_ok || !bf6_on() || !a.wb) return p;
-      p.kern = KERN_GLDS;
-      p.bm = 128;
-      p.bn = tile == TILE_BF6B_128x64 || tile == TILE_BF6R_128x64 ? 64 : 128;
-      p.ppi = 0;
-      p.tiles_m = (a.M + p.bm - 1) / p.bm;
-      return p;
-    case TILE_BF6_128x128:
-    case TILE_BF6_128x256:
-    case TILE_BF6_64x128:
-    case TILE_BF6_128x64:
-      if (!glds_ok || !bf6_on() || (tile == TILE_BF6_128x256 && a.Cout % 256)) return p;
-      p.kern = KERN_GLDS;
-      p.bm = tile == TILE_BF6_64x128 ? 64 : 128;
-      p.bn = tile == TILE_BF6_128x256 ? 256 : tile == TILE_BF6_128x64 ? 64 : 128;
-      p.ppi = 0;
-      p.tiles_m = (a.M + p.bm - 1) / p.bm;
-      return p;
-    case TILE_H8x128:
-    case TILE_H16x128:
-    case TILE_H8x64: {
-      if (!halo_ok || (tile != TILE_H8x64 && a.Cout % 128)) return p;
-      const int ph = tile == TILE_H16x128 ? 16 : 8;
-      p.kern = KERN_HALO;
-      p.bm = ph * 16;
-      p.bn = tile == TILE_H8x64 ? 64 : 128;
-      p.ppi = ((a.OW + 15) / 16) * ((a.OH + ph - 1) / ph);
-      p.tiles_m = (long long)(a.M / a.hw) * p.ppi;
-      return p;
-    }
-    case TILE_256x128:
-      if (!cin32 || a.Cout % 128) return p;
-      p.bm = 256;
-      p.bn = 128;
-      break;
-    case TILE_128x128: p.bm = 128; p.bn = 128; break;
-    case TILE_128x64: p.bm = 128; p.bn = 64; break;
-    case TILE_64x64: p.bm = 64; p.bn = 64; break;
-    default: return p;
-  }
-  // the 4-channel-input convs the G4 bf6x tile serves: it is their only
-  // candidate (its sums are not bit-identical to the staged tiles')
-  if (bf6x_on() && g4_gemm(a)) return p;
-  p.kern = !cin32 ? KERN_STAGED
-                  : (conv_env().kmax >= KERN_GLDS && a.KH * a.KW <= 32 ? KERN_GLDS : KERN_STAGED);
-  if (tile == TILE_256x128 && p.kern != KERN_GLDS) {
-    p.kern = -1;
-    return p;
-  }
-  p.ppi = 0;
-  p.tiles_m = (a.M + p.bm - 1) / p.bm;
-  return p;
-}
-
-// Default plan (heuristic), optionally overridden by a legal tile id.  The
-// split factor comes from the default choice whatever the tile, and every
-// kernel/tile runs the same fmaf sequence per output, so results do not
-// depend on the tile (the engine's autotuner relies on this).
-Plan conv_plan(const ConvArgs& a, bool allow_split, int forced = -1) {
-  const ConvEnv& env = conv_env();
-  if (forced < 0 && env.tile >= 0) forced = env.tile;  // POSFEAT_CONV_TILE: any legal tile
-  const bool cin32 = a.Cin % BK == 0;
-  const int nch = a.Kpad / BK;
-  Plan d = plan_for_tile(a, a.Cout % 128 == 0 ? TILE_H8x128 : TILE_H8x64);
-  if (d.kern == KERN_HALO) {
-    if ((env.tile == TILE_H16x128) && a.Cout % 128 == 0) d = plan_for_tile(a, TILE_H16x128);
-    const double slots = d.tile == TILE_H16x128 ? 256.0 : 512.0;
-    d.ksplit = allow_split ? choose_ksplit(d.tiles_m * ((a.Cout + d.bn - 1) / d.bn), nch, slots) : 1;
-  } else {
-    const long long t128 = (long long)((a.M + 127) / 128) * ((a.Cout + 127) / 128);
-    const long long t256 = (long long)((a.M + 255) / 256) * ((a.Cout + 127) / 128);
-    const int ks = (allow_split && a.Cout > 64) ? choose_ksplit(t128, nch, 512.0) : 1;
-    int tile;
-    if (env.tile == TILE_256x128 && cin32 && a.Cout % 128 == 0 && t256 >= 256 && ks == 1)
-      tile = TILE_256x128;
-    else if (a.Cout > 64 && (t128 >= 512 || ks > 1))
-      tile = TILE_128x128;
-    else if (cin32 && (long long)((a.M + 127) / 128) * ((a.Cout + 63) / 64) >= 512)
-      tile = TILE_128x64;  // Cin = 4 layers (stem, convimg): 64x64 measured faster
-    else
-      tile = TILE_64x64;
-    d = plan_for_tile(a, tile);
-    d.ksplit = tile == TILE_128x128 ? ks : 1;
-    if (bf6x_on() && g4_gemm(a)) {  // the stem: the G4 bf6x tile only
-      d = plan_for_tile(a, TILE_BF6X_128x64);
-      d.ksplit = 1;
-    }
-    if (bf6_on() && cin32 && a.KH * a.KW <= 32 && env.kmax >= KERN_GLDS) {
-      const bool x = bf6x_on() && dense_gemm(a);
-      Plan b = plan_for_tile(a, x ? (a.Cout > 64 ? TILE_BF6X_128x128 : TILE_BF6X_128x64)
-                                : a.wb ? (a.Cout > 64 ? TILE_BF6B_128x128 : TILE_BF6B_128x64)
-                                       : (a.Cout > 64 ? TILE_BF6_128x128 : TILE_BF6_128x64));
-      if (b.kern >= 0) {
-        b.ksplit = ks;
-        d = b;
-      }
-    }
-  }
-  // Cin % 32 convs with taps on the pre-split planes: the GT bf6x tile
-  if (bf6x_on() && gt_gemm(a) && env.kmax >= KERN_GLDS) {
-    Plan b = plan_for_tile(a, a.Cout > 64 ? TILE_BF6X_128x128 : TILE_BF6X_128x64);
-    if (b.kern >= 0) {
-      const long long t128 = (long long)((a.M + 127) / 128) * ((a.Cout + 127) / 128);
-      b.ksplit = allow_split ? choose_ksplit(t128, nch, 768.0) : 1;
-      d = b;
-    }
-  }
-  if (forced >= 0) {
-    Plan f = plan_for_tile(a, forced);
-    if (f.kern >= 0) {
-      f.ksplit = d.ksplit;
-      return f;
-    }
-  }
-  return d;
-}
-
-
-// The Cin = 4 register-staged convs (the stem) in bf16x6 with the rest of the
-// conv family (POSFEAT_BF6_STEM=0: fp32 MFMA); the train-mode backbone keeps
-// fp32 there as on its halo tiles (PfHaloFp32Scope).  All staged tiles of a
-// conv share the arithmetic, so the autotuner's choice never changes results.
-bool stem_bf6_on() {
-  static const bool off = [] {
-    const char* e = pf_ab_getenv("POSFEAT_BF6_STEM");
-    return e && e[0] == '0';
-  }();
-  return bf6_on() && !off && tl_halo_fp32 == 0 && tl_stem32 == 0;
-}
-
-template <int BM, int BN, int WM, int WN>
-void launch_rows(ConvArgs& a, int kern, hipStream_t st) {
-  dim3 grid(a.nwg * a.ksplit, a.nbatch), block(WM * WN * 64);
-  if (kern == KERN_GLDS)
-    hipLaunchKernelGGL((conv_glds_kernel<BM, BN, WM, WN>), grid, block, 0, st, a);
-  else if (a.Cin % BK == 0)
-    hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, true>), grid, block, 0, st, a);
-  else if (stem_bf6_on())
-    hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, false, true>), grid, block, 0, st, a);
-  else
-    hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, false>), grid, block, 0, st, a);
-}
-
-// A/B (POSFEAT_BF6X_BM192=1): the dense / two-source 128 x 128 bf6x plans
-// run as 192 x 128 tiles
-static bool bf6x_bm192() {
-  static const bool on = [] {
-    const char* e = pf_ab_getenv("POSFEAT_BF6X_BM192");
-    return e && e[0] == '1';
-  }();
-  return on;
+ConvShape conv_shape(const ConvArgs& a) {
+  return ConvShape{a.M, a.hw, a.OH, a.OW, a.Cin, a.xcs, a.Cout, a.KH, a.KW, a.stride, a.pad, a.Kpad,
+                   a.wb != nullptr, a.xb != nullptr, a.x2 != nullptr, a.amean != nullptr};
 }
 
 thread_local float* tl_nchw_sink = nullptr;
 thread_local bool tl_nchw_done = false;
 
-int conv_run(ConvArgs& a, const Plan& p0, hipStream_t st) {
+// Launch plan p (of conv_shape(a): the plan has already decided the kernel).
+int conv_run(ConvArgs& a, const Plan& p, hipStream_t st) {
   if (!a.zero) return POSFEAT_E_HIP;
-  Plan p = p0;
+  if (p.variant == V_NONE) return POSFEAT_E_INVALID;  // illegal tile, or a grid past INT_MAX
   // (the bf6x tiles' epilogue, conv_epilogue_t, carries the NCHW pass;
   // split-K plans write y in the reduce kernel instead)
-  const bool xt = p.tile >= TILE_BF6X_128x128 && p.tile <= TILE_BF6X_256x64;
+  const bool xt = tile_row(p.tile)->family == FAM_BF6X;
   a.ynchw = (tl_nchw_sink && xt && p.ksplit <= 1 && a.nbatch <= 1 && !a.res && a.hw % 4 == 0)
                 ? tl_nchw_sink
                 : nullptr;
   tl_nchw_done = a.ynchw != nullptr;
-  if (bf6x_bm192() && p.tile == TILE_BF6X_128x128 && p.ksplit == 1 && (dense_gemm(a) || a.x2)) {
-    const Plan q = plan_for_tile(a, TILE_BF6X_192x128);
-    if (q.kern >= 0) p = q;
-  }
-  static const bool rb4n64 = [] {  // A/B: the 128 x 64 dense / stem plans on 256 x 64 tiles
-    const char* e = pf_ab_getenv("POSFEAT_BF6X_RB4N64");
-    return e && e[0] == '1';
-  }();
-  if (rb4n64 && p.tile == TILE_BF6X_128x64 && p.ksplit == 1 && (dense_gemm(a) || g4_gemm(a)) &&
-      !a.x2) {
-    const Plan q = plan_for_tile(a, TILE_BF6X_256x64);
-    if (q.kern >= 0) p = q;
-  }
-  a.tiles_n = (a.Cout + p.bn - 1) / p.bn;
-  a.nwg = (int)(p.tiles_m * a.tiles_n);
+  a.tiles_n = p.tiles_n;
+  a.nwg = p.nwg;
   a.ksplit = p.ksplit;
-  const dim3 grid(a.nwg * a.ksplit);
-  switch (p.tile) {
-    case TILE_H8x128:
-      if (halo_bf6_on())
-        hipLaunchKernelGGL((conv_halo_kernel<8, 128, 2, 2, 3, 3, true>), grid, dim3(256), 0, st, a);
-      else
-        hipLaunchKernelGGL((conv_halo_kernel<8, 128, 2, 2, 3, 3>), grid, dim3(256), 0, st, a);
-      break;
-    case TILE_H8x64:
-      if (halo_bf6_on())
-        hipLaunchKernelGGL((conv_halo_kernel<8, 64, 2, 2, 3, 3, true>), grid, dim3(256), 0, st, a);
-      else
-        hipLaunchKernelGGL((conv_halo_kernel<8, 64, 2, 2, 3, 3>), grid, dim3(256), 0, st, a);
-      break;
-    case TILE_H16x128:
-      hipLaunchKernelGGL((conv_halo_kernel<16, 128, 4, 2, 3, 3>), grid, dim3(512), 0, st, a);
-      break;
-    case TILE_BF6_128x128:
-      hipLaunchKernelGGL((conv_glds_kernel<128, 128, 2, 2, 2, true>),
-                         dim3(a.nwg * a.ksplit, a.nbatch), dim3(256), 0, st, a);
-      break;
-    case TILE_BF6_128x256:
-      hipLaunchKernelGGL((conv_glds_kernel<128, 256, 2, 2, 2, true>), dim3(a.nwg * a.ksplit, a.nbatch),
-                         dim3(256), 0, st, a);
-      break;
-    case TILE_BF6_64x128:
-      hipLaunchKernelGGL((conv_glds_kernel<64, 128, 2, 2, 2, true>), dim3(a.nwg * a.ksplit, a.nbatch),
-                         dim3(256), 0, st, a);
-      break;
-    case TILE_BF6_128x64:
-      hipLaunchKernelGGL((conv_glds_kernel<128, 64, 2, 2, 2, true>),
-                         dim3(a.nwg * a.ksplit, a.nbatch), dim3(256), 0, st, a);
-      break;
-    case TILE_BF6X_128x128:
-      if (a.x2)  // pf_conv_dual
-        hipLaunchKernelGGL((conv_bf6x_kernel<128, 2, 3>), dim3(a.nwg * a.ksplit, a.nbatch),
-                           dim3(256), 0, st, a);
-      else if (a.amean)  // pf_conv_run_tile_np
-        hipLaunchKernelGGL((conv_bf6x_kernel<128, 2, 4>), dim3(a.nwg * a.ksplit, a.nbatch),
-                           dim3(256), 0, st, a);
-      else if (dense_gemm(a))
-        hipLaunchKernelGGL((conv_bf6x_kernel<128>), dim3(a.nwg * a.ksplit, a.nbatch), dim3(256),
-                           0, st, a);
-      else  // gt_gemm: the slab x tap gather
-        hipLaunchKernelGGL((conv_bf6x_kernel<128, 2, 2>), dim3(a.nwg * a.ksplit, a.nbatch),
-                           dim3(256), 0, st, a);
-      break;
-    case TILE_BF6X_128x64:
-      if (a.Cin == 4)  // g4_gemm: the 4-channel tap gather
-        hipLaunchKernelGGL((conv_bf6x_kernel<64, 2, 1>), dim3(a.nwg * a.ksplit, a.nbatch),
-                           dim3(256), 0, st, a);
-      else if (dense_gemm(a))
-        hipLaunchKernelGGL((conv_bf6x_kernel<64>), dim3(a.nwg * a.ksplit, a.nbatch), dim3(256), 0,
-                           st, a);
-      else
-        hipLaunchKernelGGL((conv_bf6x_kernel<64, 2, 2>), dim3(a.nwg * a.ksplit, a.nbatch),
-                           dim3(256), 0, st, a);
-      break;
-    case TILE_BF6X_128x192:  // dense GEMMs only (plan_for_tile)
-      hipLaunchKernelGGL((conv_bf6x_kernel<192>), dim3(a.nwg * a.ksplit, a.nbatch), dim3(256), 0,
-                         st, a);
-      break;
-    case TILE_BF6X_256x64:
-      if (a.Cin == 4)
-        hipLaunchKernelGGL((conv_bf6x_kernel<64, 4, 1>), dim3(a.nwg * a.ksplit, a.nbatch),
-                           dim3(256), 0, st, a);
-      else
-        hipLaunchKernelGGL((conv_bf6x_kernel<64, 4>), dim3(a.nwg * a.ksplit, a.nbatch), dim3(256),
-                           0, st, a);
-      break;
-    case TILE_BF6X_192x128:  // dense / two-source GEMMs only (plan_for_tile)
-      if (a.x2)
-        hipLaunchKernelGGL((conv_bf6x_kernel<128, 2, 3, 6>), dim3(a.nwg * a.ksplit, a.nbatch),
-                           dim3(384), 0, st, a);
-      else
-        hipLaunchKernelGGL((conv_bf6x_kernel<128, 2, 0, 6>), dim3(a.nwg * a.ksplit, a.nbatch),
-                           dim3(384), 0, st, a);
-      break;
-    case TILE_BF6X_128x256:  // dense GEMMs only (plan_for_tile)
-      hipLaunchKernelGGL((conv_bf6x_kernel<256>), dim3(a.nwg * a.ksplit, a.nbatch), dim3(256), 0,
-                         st, a);
-      break;
-    case TILE_BF6X_256x128:
-      if (dense_gemm(a))
-        hipLaunchKernelGGL((conv_bf6x_kernel<128, 4>), dim3(a.nwg * a.ksplit, a.nbatch),
-                           dim3(256), 0, st, a);
-      else
-        hipLaunchKernelGGL((conv_bf6x_kernel<128, 4, 2>), dim3(a.nwg * a.ksplit, a.nbatch),
-                           dim3(256), 0, st, a);
-      break;
-    case TILE_BF6B_128x128:
-    case TILE_BF6B_128x64: {
-      const bool wide = p.tile == TILE_BF6B_128x128;
-      if (a.xb) {  // A pre-split by its producer (pf_gemm_batched_pre)
-        const dim3 g(a.nwg * a.ksplit, a.nbatch);
-        if (wide)
-          hipLaunchKernelGGL((conv_bf6s_kernel<128, 128, 2>), g, dim3(256), 0, st, a);
-        else
-          hipLaunchKernelGGL((conv_bf6s_kernel<128, 64, 2>), g, dim3(256), 0, st, a);
-      } else if (bf6d_depth() && a.KH == 1 && a.KW == 1 && a.pad == 0) {
-        const dim3 g(a.nwg * a.ksplit, a.nbatch);
-        const int dd = bf6d_depth();
-        if (wide && dd == 2)
-          hipLaunchKernelGGL((conv_bf6d_kernel<128, 128, 2>), g, dim3(256), 0, st, a);
-        else if (wide && dd == 3)
-          hipLaunchKernelGGL((conv_bf6d_kernel<128, 128, 3>), g, dim3(256), 0, st, a);
-        else if (wide)
-          hipLaunchKernelGGL((conv_bf6d_kernel<128, 128, 4>), g, dim3(256), 0, st, a);
-        else if (dd == 2)
-          hipLaunchKernelGGL((conv_bf6d_kernel<128, 64, 2>), g, dim3(256), 0, st, a);
-        else if (dd == 3)
-          hipLaunchKernelGGL((conv_bf6d_kernel<128, 64, 3>), g, dim3(256), 0, st, a);
-        else
-          hipLaunchKernelGGL((conv_bf6d_kernel<128, 64, 4>), g, dim3(256), 0, st, a);
-      } else if (wide) {
-        hipLaunchKernelGGL((conv_bf6b_kernel<128, 128>), dim3(a.nwg * a.ksplit, a.nbatch),
-                           dim3(256), 0, st, a);
-      } else {
-        hipLaunchKernelGGL((conv_bf6b_kernel<128, 64>), dim3(a.nwg * a.ksplit, a.nbatch),
-                           dim3(256), 0, st, a);
-      }
-      break;
-    }
-    case TILE_BF6B_256x128:
-      if (bf6d_depth() == 2)
-        hipLaunchKernelGGL((conv_bf6d_kernel<256, 128, 2, 8>), dim3(a.nwg * a.ksplit, a.nbatch),
-                           dim3(512), 0, st, a);
-      else if (bf6d_depth())
-        hipLaunchKernelGGL((conv_bf6d_kernel<256, 128, 3, 8>), dim3(a.nwg * a.ksplit, a.nbatch),
-                           dim3(512), 0, st, a);
-      else
-        hipLaunchKernelGGL((conv_bf6b_kernel<256, 128, 8>), dim3(a.nwg * a.ksplit, a.nbatch),
-                           dim3(512), 0, st, a);
-      break;
-    case TILE_BF6R_128x128:
-      if (bf6d_depth()) {  // the register-A tiles: A now prefetched D chunks ahead
-        const dim3 g(a.nwg * a.ksplit, a.nbatch);
-        if (bf6d_depth() == 2)
-          hipLaunchKernelGGL((conv_bf6d_kernel<128, 128, 2>), g, dim3(256), 0, st, a);
-        else if (bf6d_depth() == 3)
-          hipLaunchKernelGGL((conv_bf6d_kernel<128, 128, 3>), g, dim3(256), 0, st, a);
-        else
-          hipLaunchKernelGGL((conv_bf6d_kernel<128, 128, 4>), g, dim3(256), 0, st, a);
-      } else {  // POSFEAT_BF6D=0: the LDS-staged form
-        hipLaunchKernelGGL((conv_bf6b_kernel<128, 128>), dim3(a.nwg * a.ksplit, a.nbatch),
-                           dim3(256), 0, st, a);
-      }
-      break;
-    case TILE_BF6R_128x64:
-      if (bf6d_depth()) {
-        const dim3 g(a.nwg * a.ksplit, a.nbatch);
-        if (bf6d_depth() == 2)
-          hipLaunchKernelGGL((conv_bf6d_kernel<128, 64, 2>), g, dim3(256), 0, st, a);
-        else if (bf6d_depth() == 3)
-          hipLaunchKernelGGL((conv_bf6d_kernel<128, 64, 3>), g, dim3(256), 0, st, a);
-        else
-          hipLaunchKernelGGL((conv_bf6d_kernel<128, 64, 4>), g, dim3(256), 0, st, a);
-      } else {
-        hipLaunchKernelGGL((conv_bf6b_kernel<128, 64>), dim3(a.nwg * a.ksplit, a.nbatch),
-                           dim3(256), 0, st, a);
-      }
-      break;
-    case TILE_256x128: launch_rows<256, 128, 4, 2>(a, p.kern, st); break;
-    case TILE_128x128: launch_rows<128, 128, 2, 2>(a, p.kern, st); break;
-    case TILE_128x64: launch_rows<128, 64, 2, 2>(a, p.kern, st); break;
-    default: launch_rows<64, 64, 2, 2>(a, p.kern, st); break;
+  const dim3 grid(a.nwg * a.ksplit, a.nbatch), block(p.threads);
+  switch (p.variant) {
+#define CONV_X(V, K) \
+  case V: hipLaunchKernelGGL(K, grid, block, 0, st, a); break;
+    CONV_VARIANTS(CONV_X)
+#undef CONV_X
+    default: return POSFEAT_E_INVALID;
   }
   PF_CHECK_LAUNCH();
-  // bf16x6: every BF6* tile, the bf16x6 halo twins and the bf16x6 stem;
-  // fp32 MFMA: the fp32 halo / row tiles
-  const bool bf6 = p.tile >= TILE_BF6_128x128 ||
-                   ((p.tile == TILE_H8x128 || p.tile == TILE_H8x64) && halo_bf6_on()) ||
-                   (p.tile < TILE_H8x128 && p.kern == KERN_STAGED && a.Cin % BK != 0 &&
-                    stem_bf6_on());
-  pf_note_arith(bf6 ? PF_ARITH_BF6 : PF_ARITH_FP32);
+  pf_note_arith(p.arith == CONV_ARITH_BF6 ? PF_ARITH_BF6 : PF_ARITH_FP32);
   if (a.ksplit > 1) {
     const long long total = (long long)a.M * (a.Cout / 4);
     long long g = (total + 255) / 256;
@@ -3218,8 +2757,8 @@ void launch_up4_weights(const float* w_packed, float* wph, hipStream_t st) {
 
 }  // namespace
 
-bool pf_bf6x_on() { return bf6x_on(); }
-bool pf_halo_bf6_on() { return halo_bf6_on(); }
+bool pf_bf6x_on() { return conv_mode().bf6x_on(); }
+bool pf_halo_bf6_on() { return conv_mode().halo_bf6_on(); }
 PfHaloFp32Scope::PfHaloFp32Scope(bool halo_fp32) : halo_(halo_fp32) {
   if (halo_) {
     ++tl_halo_fp32;
@@ -3294,11 +2833,19 @@ static int conv_prepare(const posfeat_conv_desc* d, const float* x, const float*
   a.KW = d->kw;
   a.stride = d->stride;
   a.pad = d->pad;
-  a.OH = (d->h + 2 * d->pad - d->kh) / d->stride + 1;
-  a.OW = (d->w + 2 * d->pad - d->kw) / d->stride + 1;
-  if (a.OH <= 0 || a.OW <= 0) return POSFEAT_E_INVALID;
-  a.M = d->n * a.OH * a.OW;
-  a.K = d->kh * d->kw * d->cin;
+  // M, hw, K and Kpad are ints in the kernels: formed in 64 bits (every
+  // factor is a positive int, so each product below fits) and range-checked
+  const long long oh = ((long long)d->h + 2LL * d->pad - d->kh) / d->stride + 1;
+  const long long ow = ((long long)d->w + 2LL * d->pad - d->kw) / d->stride + 1;
+  if (oh <= 0 || ow <= 0 || oh > INT_MAX || ow > INT_MAX || oh * ow > INT_MAX ||
+      d->n * (oh * ow) > INT_MAX)
+    return POSFEAT_E_INVALID;
+  const long long taps = (long long)d->kh * d->kw;
+  if (taps > INT_MAX || taps * d->cin > INT_MAX - BK) return POSFEAT_E_INVALID;  // (K padded to BK)
+  a.OH = (int)oh;
+  a.OW = (int)ow;
+  a.M = (int)(d->n * oh * ow);
+  a.K = (int)(taps * d->cin);
   a.Kpad = posfeat_conv_packed_k(d->cin, d->kh, d->kw);
   a.ycs = d->y_cstride;
   a.rcs = d->res_cstride;
@@ -3326,14 +2873,14 @@ extern "C" int posfeat_conv2d_nhwc(const posfeat_conv_desc* d, const float* x, c
                                    const float* bias, const float* res, float* y, void* stream) {
   ConvArgs a;
   PF_TRY(conv_prepare(d, x, w, bias, res, y, a));
-  return conv_run(a, conv_plan(a, false), pf_stream(stream));
+  return conv_run(a, conv_plan(conv_shape(a), conv_mode(), false), pf_stream(stream));
 }
 
 extern "C" size_t posfeat_conv2d_workspace(const posfeat_conv_desc* d) {
   ConvArgs a;
   float dummy[4] __attribute__((aligned(16)));
   if (conv_prepare(d, dummy, dummy, nullptr, nullptr, dummy, a) != POSFEAT_OK) return 0;
-  const Plan p = conv_plan(a, true);
+  const Plan p = conv_plan(conv_shape(a), conv_mode(), true);
   return p.ksplit > 1 ? (size_t)p.ksplit * a.M * a.Cout * sizeof(float) : 0;
 }
 
@@ -3344,7 +2891,7 @@ extern "C" int posfeat_conv2d_nhwc_ws(const posfeat_conv_desc* d, const float* x
   PF_TRY(conv_prepare(d, x, w, bias, res, y, a));
   const size_t need = posfeat_conv2d_workspace(d);
   const bool split = need > 0 && ws && ws_bytes >= need;
-  const Plan p = conv_plan(a, split);
+  const Plan p = conv_plan(conv_shape(a), conv_mode(), split);
   if (p.ksplit > 1) a.part = static_cast<float*>(ws);
   return conv_run(a, p, pf_stream(stream));
 }
@@ -3365,18 +2912,20 @@ extern "C" int posfeat_conv2d_nhwc_planes(const posfeat_conv_desc* d, const floa
 // Stats tiling: contiguous-row tiles may straddle two images (slot 1 holds the
 // second image's rows); patch tiles belong to one image.
 static size_t stats_tiles_per_img(const ConvArgs& a, const Plan& p) {
-  return p.ppi > 0 ? (size_t)p.ppi : (size_t)(a.hw + p.bm - 1) / p.bm + 1;
+  return p.ppi > 0 ? (size_t)p.ppi : ((size_t)a.hw + p.bm - 1) / p.bm + 1;
+}
+static size_t stats_ws_for(const ConvArgs& a, const Plan& p, int n) {
+  if (p.ppi == 0 && a.hw < p.bm) return 0;  // a tile may span > 2 images: not supported
+  const size_t nchunk = (stats_tiles_per_img(a, p) + STAT_CHUNK - 1) / STAT_CHUNK;
+  return pf_align((size_t)p.tiles_m * 2 * a.Cout * 2 * sizeof(float), 256) +
+         (size_t)n * nchunk * a.Cout * 2 * sizeof(double);
 }
 
 extern "C" size_t posfeat_conv2d_stats_workspace(const posfeat_conv_desc* d) {
   ConvArgs a;
   float dummy[4] __attribute__((aligned(16)));
   if (conv_prepare(d, dummy, dummy, nullptr, nullptr, dummy, a) != POSFEAT_OK) return 0;
-  const Plan p = conv_plan(a, false);
-  if (p.ppi == 0 && a.hw < p.bm) return 0;  // a tile may span > 2 images: not supported
-  const size_t nchunk = (stats_tiles_per_img(a, p) + STAT_CHUNK - 1) / STAT_CHUNK;
-  return pf_align((size_t)p.tiles_m * 2 * a.Cout * 2 * sizeof(float), 256) +
-         (size_t)d->n * nchunk * a.Cout * 2 * sizeof(double);
+  return stats_ws_for(a, conv_plan(conv_shape(a), conv_mode(), false), d->n);
 }
 
 extern "C" int posfeat_conv2d_nhwc_stats(const posfeat_conv_desc* d, const float* x,
@@ -3389,25 +2938,38 @@ extern "C" int posfeat_conv2d_nhwc_stats(const posfeat_conv_desc* d, const float
 
 // ---------------------------------------------------------------------------
 // Tile-aware entry points for the engine's autotuner (fmap.h).
-static const int kAllTiles[] = {TILE_H8x128,      TILE_H8x64,       TILE_128x128,
-                                TILE_128x64,      TILE_64x64,       TILE_256x128,
-                                TILE_BF6_128x128, TILE_BF6_128x256, TILE_BF6_64x128,
-                                TILE_BF6_128x64,  TILE_BF6B_128x128, TILE_BF6B_128x64,
-                                TILE_BF6R_128x128, TILE_BF6R_128x64,  TILE_BF6B_256x128,
-                                TILE_BF6X_128x128, TILE_BF6X_128x64, TILE_BF6X_128x192};
-// (TILE_BF6X_256x128 is legal where forced -- POSFEAT_CONV_TILE, the planes
-// ABI's tile argument -- but not an autotune candidate: never faster, and the
-// timing noise let it take the tap GEMM at +5 %, r7i)
-
 int pf_conv_candidates(const posfeat_conv_desc* d, int* tiles, int max, bool wplanes) {
   ConvArgs a;
   float dummy[4] __attribute__((aligned(16)));
   if (conv_prepare(d, dummy, dummy, nullptr, nullptr, dummy, a) != POSFEAT_OK) return 0;
   if (wplanes) a.wb = reinterpret_cast<const unsigned short*>(dummy);
+  const ConvShape s = conv_shape(a);
+  const ConvMode m = conv_mode();
   int n = 0;
-  for (int t : kAllTiles)
-    if (plan_for_tile(a, t).kern >= 0 && n < max) tiles[n++] = t;
+  for (const TileRow& r : kTileTable)
+    if (!r.not_candidate && plan_for_tile(s, m, r.id).kern >= 0 && n < max) tiles[n++] = r.id;
   return n;
+}
+
+int pf_conv_explain(const posfeat_conv_desc* d, bool wplanes, int tile,
+                    posfeat_conv_plan_info* out) {
+  ConvArgs a;
+  float dummy[4] __attribute__((aligned(16)));
+  if (!out) return POSFEAT_E_INVALID;
+  PF_TRY(conv_prepare(d, dummy, dummy, nullptr, nullptr, dummy, a));
+  if (wplanes) a.wb = reinterpret_cast<const unsigned short*>(dummy);
+  // (as pf_conv_run_tile with the workspace posfeat_conv2d_workspace asks for)
+  const Plan p = conv_plan(conv_shape(a), conv_mode(), posfeat_conv2d_workspace(d) > 0, tile);
+  if (p.variant == V_NONE) return POSFEAT_E_INVALID;
+  const TileRow* r = tile_row(p.run_tile);
+  *out = posfeat_conv_plan_info{p.run_tile, p.variant, variant_name(p.variant), r->bm,
+                                r->bn,      p.ksplit,  p.nwg * p.ksplit,         p.threads,
+                                p.arith};
+  return POSFEAT_OK;
+}
+extern "C" int posfeat_conv_plan_query(const posfeat_conv_desc* d, int wplanes, int tile,
+                                       posfeat_conv_plan_info* out) {
+  return pf_conv_explain(d, wplanes != 0, tile, out);
 }
 
 int pf_conv_run_tile(const posfeat_conv_desc* d, const float* x, const float* w,
@@ -3419,7 +2981,7 @@ int pf_conv_run_tile(const posfeat_conv_desc* d, const float* x, const float* w,
   a.wplane = wplane;
   const size_t need = posfeat_conv2d_workspace(d);
   const bool split = need > 0 && ws && ws_bytes >= need;
-  const Plan p = conv_plan(a, split, tile);
+  const Plan p = conv_plan(conv_shape(a), conv_mode(), split, tile);
   if (p.ksplit > 1) a.part = static_cast<float*>(ws);
   return conv_run(a, p, st);
 }
@@ -3464,9 +3026,11 @@ int pf_conv_dual(int n, int oh, int ow, const float* x1, int x1cs, int k1, const
   a.H2 = h2;
   a.W2 = w2;
   a.s2 = s2;
-  Plan p = plan_for_tile(a, TILE_BF6X_128x128);
+  const ConvShape s = conv_shape(a);
+  const ConvMode m = conv_mode();
+  const Plan p = plan_for_tile(s, m, TILE_BF6X_128x128);
   if (p.kern < 0) return POSFEAT_E_INVALID;
-  return conv_run(a, p, st);
+  return conv_run(a, plan_launch(s, m, p), st);
 }
 
 // GEMMs on the weight-stationary persistent kernel (gemm_ws_kernel):
@@ -3646,12 +3210,12 @@ int pf_conv_run_tile_np(const posfeat_conv_desc* d, const float* x, const float*
   if (!wb || !mean || !rstd || !slope || a.Kpad > 256 || d->cin != a.Kpad) return POSFEAT_E_INVALID;
   a.wb = wb;
   a.wplane = wplane;
-  const Plan p = conv_plan(a, false, tile);
-  if (p.tile != TILE_BF6X_128x128 || p.ksplit != 1 || !dense_gemm(a) || bf6x_bm192())
-    return POSFEAT_E_UNSUPPORTED;
   a.amean = mean;
   a.arstd = rstd;
   a.aslope = slope;
+  const ConvShape s = conv_shape(a);
+  const Plan p = conv_plan(s, conv_mode(), false, tile);
+  if (p.variant != V_X128_NORM || p.ksplit != 1 || !dense_gemm(s)) return POSFEAT_E_UNSUPPORTED;
   return conv_run(a, p, st);
 }
 
@@ -3715,12 +3279,12 @@ int pf_conv_run_tile_bn(const posfeat_conv_desc* d, const float* x, const float*
   a.wplane = wplane;
   const size_t need = posfeat_conv2d_workspace(d);
   const bool split = need > 0 && ws && ws_bytes >= need;
-  const Plan p = conv_plan(a, split, tile);
+  const Plan p = conv_plan(conv_shape(a), conv_mode(), split, tile);
   if (p.ksplit > 1) {
     a.part = static_cast<float*>(ws);
   } else if (part && p.tiles_m * 2 * (size_t)a.Cout * sizeof(double) <= part_bytes &&
              p.tiles_m <= 0x7fffffff &&
-             !(p.tile >= TILE_BF6X_128x128 && p.tile <= TILE_BF6X_256x64)) {
+             tile_row(p.tile)->family != FAM_BF6X) {
     a.bnpart = part;
     *nparts = (int)p.tiles_m;
   }
@@ -3729,21 +3293,16 @@ int pf_conv_run_tile_bn(const posfeat_conv_desc* d, const float* x, const float*
   return rc;
 }
 
-static size_t stats_ws_for(const ConvArgs& a, const Plan& p, int n) {
-  if (p.ppi == 0 && a.hw < p.bm) return 0;
-  const size_t nchunk = (stats_tiles_per_img(a, p) + STAT_CHUNK - 1) / STAT_CHUNK;
-  return pf_align((size_t)p.tiles_m * 2 * a.Cout * 2 * sizeof(float), 256) +
-         (size_t)n * nchunk * a.Cout * 2 * sizeof(double);
-}
-
 size_t pf_conv_stats_ws_max(const posfeat_conv_desc* d) {
   ConvArgs a;
   float dummy[4] __attribute__((aligned(16)));
   if (conv_prepare(d, dummy, dummy, nullptr, nullptr, dummy, a) != POSFEAT_OK) return 0;
   size_t mx = 0;
-  for (int t : kAllTiles) {
-    const Plan p = plan_for_tile(a, t);
-    if (p.kern < 0) continue;
+  const ConvShape s = conv_shape(a);
+  const ConvMode m = conv_mode();
+  for (const TileRow& r : kTileTable) {
+    const Plan p = plan_for_tile(s, m, r.id);
+    if (r.not_candidate || p.kern < 0) continue;
     const size_t s = stats_ws_for(a, p, d->n);
     if (s > mx) mx = s;
   }
@@ -3758,7 +3317,7 @@ int pf_conv_stats_run_tile(const posfeat_conv_desc* d, const float* x, const flo
   PF_TRY(conv_prepare(d, x, w, bias, nullptr, y, a));
   a.wb = wb;
   a.wplane = wplane;
-  const Plan p = conv_plan(a, false, tile);
+  const Plan p = conv_plan(conv_shape(a), conv_mode(), false, tile);
   const size_t need = stats_ws_for(a, p, d->n);
   if (need == 0) return POSFEAT_E_UNSUPPORTED;
   if (!ws || ws_bytes < need || !mean || !rstd) return POSFEAT_E_WORKSPACE;
@@ -3839,7 +3398,7 @@ int pf_up4_gconv(int n, int H, int W, const float* G, int gcs, const float* wph,
   d.act = POSFEAT_ACT_NONE;
   ConvArgs g;
   PF_TRY(conv_prepare(&d, G, wg, bias, nullptr, y, g));
-  return conv_run(g, conv_plan(g, false), st);
+  return conv_run(g, conv_plan(conv_shape(g), conv_mode(), false), st);
 }
 
 int pf_up4_border(int n, int H, int W, const float* L, int lcs, const float* wph, float* y,
@@ -3947,7 +3506,8 @@ int pf_gemm_batched_pre(const unsigned short* Ab, int lda, long long pa, long lo
   a.wplane = bplane;
   a.xb = Ab;
   a.xplane = pa;
-  const Plan p = conv_plan(a, false, N % 128 == 0 ? TILE_BF6B_128x128 : TILE_BF6B_128x64);
+  const Plan p = conv_plan(conv_shape(a), conv_mode(), false,
+                           N % 128 == 0 ? TILE_BF6B_128x128 : TILE_BF6B_128x64);
   if (p.tile != TILE_BF6B_128x128 && p.tile != TILE_BF6B_128x64) return POSFEAT_E_UNSUPPORTED;
   a.nbatch = nb;
   a.bxb = sa;
@@ -3960,18 +3520,13 @@ int pf_gemm_batched(const float* A, int lda, long long sa, const float* B, long 
                     int ldc, long long sc, int nb, int M, int N, int K, hipStream_t st,
                     const unsigned short* Bb, long long bplane) {
   if (K % BK || N % 4 || nb < 1) return POSFEAT_E_INVALID;
-  // the short-K batched GEMMs on the weight-stationary kernel: head.conv1's
-  // (K = 192), layer2's and layer3's conv2 (K = 128, 256) Winograd GEMMs
-  // (r16zz4, B = 32, two runs: 0.628 -> 0.484, 0.087 -> 0.076, 0.078 -> 0.070
-  // ms; bit-identical).  A/B POSFEAT_WSB: 0 off, 1 K = 192 only, 2 K <= 192
-  static const int wsb = [] {
-    const char* e = pf_ab_getenv("POSFEAT_WSB");
-    return e ? atoi(e) : 3;
-  }();
-  if (wsb && Bb && bf6x_on() && pf_gemm_ws_batched_ok(K, N) && lda % 4 == 0 &&
-      (K == 192 || (K == 128 && wsb >= 2) || (K == 256 && wsb >= 3))) {
+  // the short-K batched GEMMs on the weight-stationary kernel first
+  // (gemm_batched_ws_first), the rest and what it declines on the tiles below
+  ConvMode mode = conv_mode();
+  if (gemm_batched_ws_first(K, Bb != nullptr, mode) && pf_gemm_ws_batched_ok(K, N) &&
+      lda % 4 == 0) {
     const int r = pf_gemm_ws_batched(A, lda, sa, Bb, bplane, sb, C, ldc, sc, nb, M, N, K, st);
-    if (r != POSFEAT_E_UNSUPPORTED) return r;  // (else: the bf6x tiles below)
+    if (r != POSFEAT_E_UNSUPPORTED) return r;
   }
   posfeat_conv_desc d;
   d.n = 1;
@@ -3990,60 +3545,12 @@ int pf_gemm_batched(const float* A, int lda, long long sa, const float* B, long 
   PF_TRY(conv_prepare(&d, A, B, nullptr, nullptr, C, a));
   a.wb = Bb;  // B as three bf16 planes (plane stride bplane, batch stride sb)
   a.wplane = bplane;
-  // the heuristic sizes tiles for ONE GEMM; with nb of them in the grid the
-  // 128x128 tile (2x the operand reuse of 64x64) still fills the chip
-  const long long t128 = (long long)((M + 127) / 128) * ((N + 127) / 128) * nb;
-  // N = 192 (head.conv1's Winograd GEMMs) on pre-split planes: three 64-wide
-  // column tiles instead of two 128-wide ones, the second of them half empty
-  // POSFEAT_GEMM_B256=1 (A/B): the 8-wave 256x128 pre-split tiles
-  static const bool b256 = [] {
-    const char* e = pf_ab_getenv("POSFEAT_GEMM_B256");
-    return e && e[0] == '1';
-  }();
-  // POSFEAT_TRAIN_WINO_BF6X=1 (A/B, off): the train-mode backbone's batched
+  // POSFEAT_TRAIN_WINO_BF6X=1 (A/B): the train-mode backbone's batched
   // (Winograd decoder) GEMMs on the 16x16x32 tiles too, its halo scope lifted
-  // for them.  The fp64 fixture step's per-tensor errors unchanged to the
-  // digits shown; same-box train_desc +0.5..2 % over four pairs, but the
-  // four decoder GEMM launches 1704 us (32x32x16, r15e) vs 1718 us (16x16x32,
-  // r15j) per set and the per-label breakdown flat: not the
-  // default.
-  static const bool twx = [] {
-    const char* e = pf_ab_getenv("POSFEAT_TRAIN_WINO_BF6X");
-    return e && e[0] == '1';
-  }();
-  struct HaloLift {  // the calling thread's halo scope lifted for this call
-    int saved;
-    bool on;
-    explicit HaloLift(bool o) : saved(tl_halo_fp32), on(o) {
-      if (on) tl_halo_fp32 = 0;
-    }
-    ~HaloLift() {
-      if (on) tl_halo_fp32 = saved;
-    }
-  } const lift(twx && Bb);
-  const bool x = Bb && bf6x_on();
-  // POSFEAT_BF6X_RB4=1 (A/B): the 256-row 16x16x32 tiles for the batched GEMMs
-  static const bool rb4 = [] {
-    const char* e = pf_ab_getenv("POSFEAT_BF6X_RB4");
-    return e && e[0] == '1';
-  }();
-  // N = 192 (head.conv1): one 192-wide column tile reads A once (three
-  // 64-wide tiles read it three times)
-  // POSFEAT_BF6X_N256=1 (A/B): one 256-wide column tile for N % 256 == 0
-  // (the decoder's Winograd GEMMs: A read once per 256 columns, not twice)
-  static const bool n256 = [] {
-    const char* e = pf_ab_getenv("POSFEAT_BF6X_N256");
-    return e && e[0] == '1';
-  }();
-  const int want = x ? (n256 && N % 256 == 0 ? TILE_BF6X_128x256
-                        : N % 128 == 0 ? (rb4 ? TILE_BF6X_256x128 : TILE_BF6X_128x128)
-                        : N % 192 == 0 ? TILE_BF6X_128x192
-                                       : TILE_BF6X_128x64)
-                   : (Bb && b256 && N % 128 == 0) ? TILE_BF6B_256x128
-                   : (N % 128 == 0 && t128 >= 1024) ? TILE_128x128
-                   : (Bb && N % 128 != 0 && N % 64 == 0) ? TILE_BF6B_128x64
-                                                                 : -1;
-  const Plan p = conv_plan(a, false, want);
+  // for this call
+  if (mode.train_wino_bf6x && Bb) mode.halo_fp32 = false;
+  const Plan p = conv_plan(conv_shape(a), mode, false,
+                           gemm_batched_tile(M, N, nb, Bb != nullptr, mode));
   if (p.kern != KERN_GLDS) return POSFEAT_E_UNSUPPORTED;
   a.nbatch = nb;
   a.bx = sa;

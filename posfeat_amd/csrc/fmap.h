@@ -38,6 +38,10 @@ int pf_up4_main(int n, int H, int W, const float* L, int lcs, const float* wph, 
 // wplanes / wb: the weights also exist as three bf16 planes of w's layout
 // (plane stride wplane elements): enables the pre-split bf16x6 tiles
 int pf_conv_candidates(const posfeat_conv_desc* d, int* tiles, int max, bool wplanes = false);
+// the plan pf_conv_run_tile(d, ..., tile) takes given the workspace it asks
+// for (host only: no device needed, nothing launched)
+int pf_conv_explain(const posfeat_conv_desc* d, bool wplanes, int tile,
+                    posfeat_conv_plan_info* out);
 int pf_conv_run_tile(const posfeat_conv_desc* d, const float* x, const float* w,
                      const float* bias, const float* res, float* y, void* ws, size_t ws_bytes,
                      int tile, hipStream_t st, const unsigned short* wb = nullptr,

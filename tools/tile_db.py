@@ -12,6 +12,14 @@ adds those entries: it loads the current database, runs the descriptor-training
 step at the bench shapes with POSFEAT_TRAIN_TUNE_LIVE=1 and writes the union.
 
 usage: python tools/tile_db.py [--train] [out]   (GPU box)
+       python tools/tile_db.py --explain B H W    (any box: planning needs no device)
+
+--explain prints the conv planner's launch plan (conv_plan.h through
+posfeat_conv_plan_query) for every encoder / decoder / head conv at batch B
+and image H x W, as a direct conv with pre-split weight planes and no forced
+tile.  (The engine runs some of these layers by other routes -- Winograd, the
+weight-stationary GEMMs, the fused downsample and tap forms -- whose batched
+GEMMs go through the same planner with their own shapes.)
 """
 import os
 import sys
@@ -65,7 +73,56 @@ def train_main(out):
     print("%d entries -> %s (%.1f s)" % (n, out, time.perf_counter() - t0))
 
 
+def layer_convs(B, H, W):
+    """[(name, n, h, w, cin, cout, k, stride)]: every conv of the engine's layer
+    table with the geometry its forward runs it at (engine.hip)."""
+    from posfeat_amd import _lib
+    h2, w2 = (H - 1) // 2 + 1, (W - 1) // 2 + 1      # 7x7 stride 2 pad 3
+    h4, w4 = (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1    # maxpool 3 stride 2 pad 1
+    h8, w8 = (h4 - 1) // 2 + 1, (w4 - 1) // 2 + 1
+    h16, w16 = (h8 - 1) // 2 + 1, (w8 - 1) // 2 + 1
+    fixed = {"firstconv": (H, W, 2), "conv_coarse": (h16, w16, 1), "upconv3.conv": (h8, w8, 1),
+             "iconv3": (h8, w8, 1), "upconv2.conv": (h4, w4, 1), "iconv2": (h4, w4, 1),
+             "conv_fine": (h4, w4, 1), "head.conv1": (h4, w4, 1), "head.convimg": (H, W, 1),
+             "head.conv2": (H, W, 1), "head.conv3": (H, W, 1)}
+    stage_in = {1: (h4, w4, 1), 2: (h4, w4, 2), 3: (h8, w8, 2)}
+    out = []
+    for name, cout, cin, kh, kw, _, _ in _lib.model_specs():
+        if kh == 0:
+            continue   # head.prelu
+        if name in fixed:
+            h, w, st = fixed[name]
+        else:          # layerL.B.part: block 0 carries the stage's stride in conv2 / downsample
+            stage, blk, part = name[5:].split(".")
+            h, w, s0 = stage_in[int(stage)]
+            st = s0 if (blk == "0" and part in ("conv2", "downsample")) else 1
+            if blk != "0" or part == "conv3":
+                h, w = (h - 1) // s0 + 1, (w - 1) // s0 + 1
+        out.append((name, B, h, w, cin, cout, kh, st))
+    return out
+
+
+def explain_main(B, H, W):
+    from posfeat_amd import _lib
+    print("conv plans at B %d, %d x %d (conv precision %d, weight planes, no forced tile)"
+          % (B, H, W, _lib.lib().posfeat_set_conv_precision(-1)))
+    print("%-18s %-22s %4s %9s %7s %6s %6s %5s  %s" % ("layer", "n x h x w  cin->cout k/s",
+                                                    "tile", "bm x bn", "ksplit", "grid", "block",
+                                                    "arith", "kernel"))
+    for name, n, h, w, cin, cout, k, st in layer_convs(B, H, W):
+        shape = "%dx%dx%d %d->%d %d/%d" % (n, h, w, cin, cout, k, st)
+        p = _lib.conv_plan_query(n, h, w, cin, (cout + 3) // 4 * 4, k, st, k // 2, wplanes=True)
+        if p is None:
+            print("%-18s %-22s rejected" % (name, shape))
+            continue
+        print("%-18s %-22s %4d %9s %7d %6d %6d %5s  %s"
+              % (name, shape, p["tile"], "%d x %d" % (p["bm"], p["bn"]), p["ksplit"], p["grid"],
+                 p["block"], "bf16x6" if p["arith"] else "fp32", p["kernel"]))
+
+
 def main():
+    if ARGS and ARGS[0] == "--explain":
+        return explain_main(*[int(a) for a in ARGS[1:4]])
     from posfeat_amd.engine import ExtractionEngine, tile_db_export
     from posfeat_amd.weights import seeded_state_dicts
     out = ARGS[0] if ARGS else os.path.join(ROOT, "records", "tile_db.txt")
