@@ -684,6 +684,60 @@ int posfeat_reproj_hist(const float *kp, const int32_t *set_off, int nsets, cons
                         const double *H, int nthr, int32_t *hist, void *ws, size_t ws_bytes,
                         void *stream);
 
+/* RANSAC homographies for every pair of a list, on the matches
+ * posfeat_match_pairs left (no reference counterpart: the consumers of the
+ * reference's matches call OpenCV on the host, one pair at a time).  kp,
+ * set_off, pairs, matches and counts mean what they mean for
+ * posfeat_reproj_hist.  Per pair p (its position in `pairs`), with n =
+ * counts[p] matches, all in fp64:
+ *   sampler      iteration `it` draws the four distinct match indices
+ *                posfeat_ransac_sample(seed, p, it, n) gives: with mix() the
+ *                splitmix64 finaliser, r = mix(mix(mix(seed ^ mix(p)) ^ it) ^ k),
+ *                j = ((r >> 32) (n - k)) >> 32, then ++j for every earlier draw
+ *                <= j taken in ascending order (k = 0..3);
+ *   degeneracy   for each of the four point triples (i, j, k) of the sample, in
+ *                each image, in pixels: cr = (pj - pi) x (pk - pi); the sample
+ *                is rejected when |cr| <= 1e-6 |pj - pi| |pk - pi| or the sign
+ *                of cr differs between the images;
+ *   solve        the 8x8 system for h11..h32 (h33 = 1) in coordinates
+ *                normalised per pair and per side over all its matches
+ *                (centroid 0, mean distance sqrt 2), Gaussian elimination with
+ *                partial pivoting, a pivot below 1e-12 times the largest entry
+ *                of its column rejecting the sample; H = T2^-1 Hn T1;
+ *   score        the residual of posfeat_reproj_hist: a match is an inlier iff
+ *                its distance is finite and <= thr;
+ *   selection    most inliers, ties to the lowest iteration; rejected samples
+ *                never win;
+ *   refit        least squares over the winner's inliers (same parametrisation
+ *                and coordinates, normal equations accumulated in a fixed
+ *                order), kept iff its inlier count is >= the winner's.
+ * Outputs (device): H [npairs][9] row-major, Frobenius norm 1, H[8] >= 0;
+ * info [npairs][4] = {status, n_inliers, best_iter, refit_kept}; inlier
+ * [sum n1] uint8: inlier[moff[p] + i] = 1 iff match i < counts[p] of pair p is
+ * an inlier of H[p], the pair's other rows 0.  status 1 (fewer than 4 matches,
+ * or every sample rejected): H[p] = 0, n_inliers 0, best_iter -1, mask 0.  A
+ * match with an index outside its set is never an inlier and takes no part in
+ * the normalisation.
+ * Returns, before any device work: POSFEAT_E_INVALID for a null pointer, a set
+ * index out of range, a negative or decreasing set_off, sum n1 past INT32_MAX,
+ * iters outside 1..65536, a non-finite or non-positive thr;
+ * POSFEAT_E_WORKSPACE for ws_bytes below posfeat_ransac_homography_workspace
+ * (0 for an invalid table or iteration count).  ws must be 256-B aligned.
+ * Three launches whatever npairs; stream-ordered, never synchronises the host;
+ * NOT graph-capturable (the pair table is copied from pageable host memory).
+ * Deterministic: the same inputs give the same bits, and the result for a
+ * pair index does not depend on the other pairs of the list.
+ * posfeat_ransac_sample is host only (no device, no launch): the sampler the
+ * kernels call; POSFEAT_E_INVALID for n < 4. */
+int posfeat_ransac_sample(uint64_t seed, int pair, int iter, int n, int32_t out4[4]);
+size_t posfeat_ransac_homography_workspace(const int32_t *set_off, int nsets,
+                                           const int32_t *pairs, int npairs, int iters);
+int posfeat_ransac_homography(const float *kp, const int32_t *set_off, int nsets,
+                              const int32_t *pairs, int npairs, const int32_t *matches,
+                              const int32_t *counts, int iters, double thr, uint64_t seed,
+                              double *H, int32_t *info, uint8_t *inlier, void *ws,
+                              size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
