@@ -738,6 +738,122 @@ int posfeat_ransac_homography(const float *kp, const int32_t *set_off, int nsets
                               double *H, int32_t *info, uint8_t *inlier, void *ws,
                               size_t ws_bytes, void *stream);
 
+/* RANSAC fundamental matrices for every pair of a list: the two-view
+ * geometric verification the reference's Aachen and ETH pipelines hand to
+ * COLMAP (evaluations/aachen/reconstruct_pipeline.py:224-231), on the matches
+ * posfeat_match_pairs left.  kp, set_off, pairs, matches, counts, iters, thr,
+ * seed, ws and stream mean what they mean for posfeat_ransac_homography.  Per
+ * pair p with n = counts[p] matches, all in fp64, x1 = (x, y, 1) the image-1
+ * point and x2 = (u, v, 1) the image-2 point of a match:
+ *   sampler      iteration `it` draws the seven distinct match indices
+ *                posfeat_ransac_sample_k(seed, p, it, n, 7, out) gives: the scheme
+ *                of posfeat_ransac_sample continued to k = 0..6 (same mix, same
+ *                base, ++j for every earlier draw <= j taken in ascending
+ *                order), so its first four draws are that call's.  A sample
+ *                holding a match with an index outside its set is rejected;
+ *   coordinates  per pair and per side Ti = [s 0 -s cx; 0 s -s cy; 0 0 1]:
+ *                centroid 0, mean distance sqrt 2 over all matches whose
+ *                indices are inside their sets (posfeat_ransac_homography's);
+ *   system       row i of the 7x9 system A f = 0 is (u x, u y, u, v x, v y, v,
+ *                x, y, 1) of sample match i in normalised coordinates, f = Fn
+ *                row-major (x2^T Fn x1 = 0);
+ *   null space   Gaussian elimination with full pivoting: step s = 0..6 takes
+ *                the largest |A[r][c]| over r >= s, c >= s (the first in
+ *                row-major order on a tie), swaps it to (s, s) by a row and a
+ *                column swap, and subtracts A[r][s] / A[s][s] times row s from
+ *                every row r > s.  The sample is rejected when a pivot is below
+ *                1e-12 times the largest |entry| of the system as given, or is
+ *                not a positive number (a null space of more than two
+ *                dimensions, e.g. a repeated match).  The two columns left at
+ *                positions 7 and 8 are free: f1 has z = (1, 0) there, f2 has
+ *                z = (0, -1), the other entries by back substitution (z[c] =
+ *                -(A[c][7] z[7] + A[c][8] z[8] + sum_{c<k<7} A[c][k] z[k]) /
+ *                A[c][c], c = 6..0), then the column swaps undone.  No entry of
+ *                F is fixed, so F33 = 0 (pure forward motion) is an ordinary
+ *                case; and with -1 in f2 the member of the pencil below that no
+ *                finite l reaches is the one whose two free entries are equal,
+ *                not the one whose free entries are opposite (every
+ *                skew-symmetric F, i.e. every pure translation, when the free
+ *                columns are a transposed pair);
+ *   cubic        det(l f1 + (1 - l) f2) = det(B + l D), B = f2, D = f1 - f2, = c0
+ *                + c1 l + c2 l^2 + c3 l^3 where ck sums the determinants with k
+ *                rows taken from D and the others from B;
+ *   roots        with cm = max |ck|: |c3| > 1e-12 cm: the monic cubic l^3 + a l^2
+ *                + b l + d in closed form, Q = (a^2 - 3 b) / 9, R = (2 a^3 - 9 a b
+ *                + 27 d) / 54; for R^2 < Q^3 the three roots -2 sqrt(Q) cos((t +
+ *                2 pi k) / 3) - a / 3, t = acos(R / sqrt(Q^3)), k = 0, 1, -1, else
+ *                the one root A + Q / A - a / 3 with A = -sign(R) cbrt(|R| +
+ *                sqrt(R^2 - Q^3)) (Q / A read as 0 for A = 0); each root then
+ *                takes two Newton steps on the monic cubic (a step with a zero
+ *                derivative or a non-finite result is skipped).  Otherwise
+ *                (leading coefficient <= 1e-12 cm) the quadratic c2 l^2 + c1 l +
+ *                c0: q = -(c1 + sign(c1) sqrt(c1^2 - 4 c2 c0)) / 2, roots q / c2
+ *                and c0 / q, none for a negative discriminant; with |c2| <=
+ *                1e-12 cm too, the root -c0 / c1 if |c1| > 1e-12 cm, else none.
+ *                The real roots in ascending l are candidates r = 0, 1, 2: Fn =
+ *                l f1 + (1 - l) f2, F = T2^T Fn T1.  A sample without a real
+ *                root counts as rejected;
+ *   score        the squared Sampson distance in pixels, d2 = (x2^T F x1)^2 /
+ *                ((F x1)_1^2 + (F x1)_2^2 + (F^T x2)_1^2 + (F^T x2)_2^2); a
+ *                match is an inlier iff d2 is finite and <= thr^2, evaluated
+ *                without the division as e^2 <= thr^2 den with thr^2 den finite
+ *                and den > 0;
+ *   selection    most inliers, ties to the lowest iteration, then to the lowest
+ *                root index; rejected samples never win;
+ *   refit        the normalised 8-point fit over the winner's inliers: N = sum
+ *                of a a^T over the inliers' rows a (as in `system`), accumulated
+ *                in a fixed order; its eigenvectors by cyclic Jacobi: a sweep
+ *                visits (p, q), p < q, in row-major order, and for Npq != 0
+ *                rotates with theta = (Nqq - Npp) / (2 Npq), t = sign(theta) /
+ *                (|theta| + sqrt(theta^2 + 1)) (sign(0) = +1), c = 1 / sqrt(t^2 +
+ *                1), s = t c; sweeps run while the sum of the squared
+ *                off-diagonal entries above the diagonal exceeds 1e-32 times the
+ *                sum of the squared diagonal entries, 16 at the most.  Fn = the
+ *                eigenvector of the lowest diagonal entry (the first on a tie).
+ *                Rank 2: the same Jacobi on Fn^T Fn (3x3), w = the eigenvector of
+ *                its lowest eigenvalue, Fn <- Fn - (Fn w) w^T, which zeroes the
+ *                smallest singular value.  F = T2^T Fn T1 is kept iff the
+ *                winner has at least 8 inliers (fewer leave the fit
+ *                under-determined), F is finite and not all zero, and its
+ *                inlier count is >= the winner's.
+ * Outputs (device): F [npairs][9] row-major, Frobenius norm 1, the entry of
+ * largest magnitude positive (the first such entry on a tie); info [npairs][4]
+ * = {status, n_inliers, best_iter, refit_kept | root << 8} with root the
+ * winning candidate's index; inlier [sum n1] uint8 laid out as
+ * posfeat_ransac_homography's.  status 1 (fewer than 7 matches, or every sample
+ * rejected): F[p] = 0, info {1, 0, -1, 0}, mask 0.
+ * Returns, before any device work: POSFEAT_E_INVALID for a null pointer, a set
+ * index out of range, a negative or decreasing set_off, sum n1 past INT32_MAX,
+ * iters outside 1..65536, a non-finite or non-positive thr;
+ * POSFEAT_E_WORKSPACE for ws_bytes below posfeat_ransac_fundamental_workspace
+ * (0 for an invalid table or iteration count).  ws must be 256-B aligned.
+ * Three launches whatever npairs; stream-ordered, never synchronises the host;
+ * NOT graph-capturable (the pair table is copied from pageable host memory).
+ * Deterministic: the same inputs give the same bits, and the result for a
+ * pair index does not depend on the other pairs of the list.
+ * Limitation: a planar scene or a pure rotation is degenerate for F (the
+ * epipolar system of its inliers has a three-dimensional null space, and any
+ * member fits them).  The call does not detect this; such pairs are what
+ * posfeat_ransac_homography is for.
+ * posfeat_ransac_sample_k and posfeat_fundamental_solve7 are host only (no
+ * device, no launch).  posfeat_ransac_sample_k writes the first k draws (4 <= k
+ * <= 8) of the sampler to out[k]; POSFEAT_E_INVALID for n < k, a null out, k
+ * out of range, a negative pair or iter.  posfeat_fundamental_solve7 runs
+ * `system` to `roots` on m [7][4] = (x, y, u, v) rows already in normalised
+ * coordinates, writes the candidates Fn to F [<= 3][9], each scaled as the
+ * outputs above, and returns their number: 0 for a rejected sample,
+ * POSFEAT_E_INVALID for a null pointer.  It compiles the text the kernels
+ * compile, with the host's acos / cos / cbrt. */
+int posfeat_ransac_sample_k(uint64_t seed, int pair, int iter, int n, int k, int32_t *out);
+int posfeat_fundamental_solve7(const double *m, double *F);
+size_t posfeat_ransac_fundamental_workspace(const int32_t *set_off, int nsets,
+                                            const int32_t *pairs, int npairs, int iters);
+int posfeat_ransac_fundamental(const float *kp, const int32_t *set_off, int nsets,
+                               const int32_t *pairs, int npairs, const int32_t *matches,
+                               const int32_t *counts, int iters, double thr, uint64_t seed,
+                               double *F, int32_t *info, uint8_t *inlier, void *ws,
+                               size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

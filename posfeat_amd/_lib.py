@@ -220,6 +220,13 @@ SIGNATURES = {
                                     c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "posfeat_ransac_sample": (c_int, [ctypes.c_uint64, c_int, c_int, c_int, c_void_p]),
     "posfeat_ransac_homography_workspace": (c_size_t, [c_void_p, c_int, c_void_p, c_int, c_int]),
+    "posfeat_ransac_sample_k": (c_int, [ctypes.c_uint64, c_int, c_int, c_int, c_int, c_void_p]),
+    "posfeat_fundamental_solve7": (c_int, [c_void_p, c_void_p]),
+    "posfeat_ransac_fundamental_workspace": (c_size_t, [c_void_p, c_int, c_void_p, c_int, c_int]),
+    "posfeat_ransac_fundamental": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                           c_void_p, c_int, ctypes.c_double, ctypes.c_uint64,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                           c_void_p]),
     "posfeat_ransac_homography": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                           c_void_p, c_int, ctypes.c_double, ctypes.c_uint64,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,

@@ -4,7 +4,8 @@
 // whole list, as that call left them on the device, go through three launches
 // whatever the number of pairs:
 //
-//   ransac_gather_kernel  one workgroup per pair: the matched keypoints
+//   ransac_gather_kernel  (ransac_gather.h, shared with fundamental.hip) one
+//                         workgroup per pair: the matched keypoints
 //                         gathered into a compact (x1 y1 x2 y2) fp32 row per
 //                         match, and the two normalisations (centroid, mean
 //                         distance sqrt 2) reduced in fp64 in a fixed order.
@@ -47,9 +48,7 @@ using namespace pfransac_plan;
 static_assert(sizeof(Pair) == 32, "device table layout");
 static_assert(RBLOCK == 256 && RTILE == 256, "one staged match per thread of a workgroup");
 
-struct Norm {
-  double cx1, cy1, s1, cx2, cy2, s2;
-};
+#include "ransac_gather.h"  // Norm, block_reduce, pair_count, ransac_gather_kernel, load_norm
 
 // Gaussian elimination with partial pivoting on the augmented 8x9 system, in
 // place; x = the solution.  False when a pivot is below 1e-12 times the largest
@@ -177,92 +176,6 @@ __device__ __forceinline__ bool is_inlier(const double (&H)[9], double x, double
 }
 __device__ __forceinline__ bool is_inlier(const double (&H)[9], const float4& m, double thr2) {
   return is_inlier(H, (double)m.x, (double)m.y, (double)m.z, (double)m.w, thr2);
-}
-
-// fixed-order tree over the 256 threads; every thread gets the result
-template <class T, class Op>
-__device__ __forceinline__ T block_reduce(T v, T* red, Op op) {
-  const int tid = threadIdx.x;
-  __syncthreads();  // red may still be read from the call before
-  red[tid] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = RBLOCK / 2; s > 0; s >>= 1) {
-    if (tid < s) red[tid] = op(red[tid], red[tid + s]);
-    __syncthreads();
-  }
-  return red[0];
-}
-struct OpAdd {
-  template <class T>
-  __device__ T operator()(T a, T b) const { return a + b; }
-};
-struct OpMax {
-  template <class T>
-  __device__ T operator()(T a, T b) const { return a > b ? a : b; }
-};
-
-__device__ __forceinline__ int pair_count(const int* __restrict__ counts, int p, const Pair& q) {
-  return max(0, min(counts[p], q.n1));
-}
-
-__global__ __launch_bounds__(256) void ransac_gather_kernel(const float* __restrict__ kp,
-                                                            const Pair* __restrict__ tab,
-                                                            const int* __restrict__ matches,
-                                                            const int* __restrict__ counts,
-                                                            float4* __restrict__ pts,
-                                                            double* __restrict__ norm) {
-  __shared__ double red[RBLOCK];
-  __shared__ int ired[RBLOCK];
-  const int p = blockIdx.x, tid = threadIdx.x;
-  const Pair q = tab[p];
-  const int n = pair_count(counts, p, q);
-  if (n == 0) return;
-  const int* mp = matches + 2 * (long long)q.moff;
-  float4* op = pts + q.moff;
-  double sx1 = 0, sy1 = 0, sx2 = 0, sy2 = 0;
-  int nv = 0;
-  for (int i = tid; i < n; i += RBLOCK) {
-    const int ia = mp[2 * i], ib = mp[2 * i + 1];
-    // a match outside its sets is kept as a NaN row: never sampled into a
-    // hypothesis that survives, never an inlier, not part of the normalisation
-    float4 m = make_float4(NAN, NAN, NAN, NAN);
-    if ((unsigned)ia < (unsigned)q.n1 && (unsigned)ib < (unsigned)q.n2) {
-      const float* pa = kp + 2 * ((long long)q.a_off + ia);
-      const float* pb = kp + 2 * ((long long)q.b_off + ib);
-      m = make_float4(pa[0], pa[1], pb[0], pb[1]);
-      sx1 += (double)m.x, sy1 += (double)m.y, sx2 += (double)m.z, sy2 += (double)m.w;
-      ++nv;
-    }
-    op[i] = m;
-  }
-  const double cnt = (double)block_reduce(nv, ired, OpAdd());
-  Norm nm;
-  nm.cx1 = block_reduce(sx1, red, OpAdd()) / cnt;
-  nm.cy1 = block_reduce(sy1, red, OpAdd()) / cnt;
-  nm.cx2 = block_reduce(sx2, red, OpAdd()) / cnt;
-  nm.cy2 = block_reduce(sy2, red, OpAdd()) / cnt;
-  double d1 = 0, d2 = 0;
-  for (int i = tid; i < n; i += RBLOCK) {
-    const float4 m = op[i];  // this thread's own rows
-    if (m.x != m.x) continue;
-    const double ax = (double)m.x - nm.cx1, ay = (double)m.y - nm.cy1;
-    const double bx = (double)m.z - nm.cx2, by = (double)m.w - nm.cy2;
-    d1 += sqrt(ax * ax + ay * ay);
-    d2 += sqrt(bx * bx + by * by);
-  }
-  nm.s1 = sqrt(2.0) / (block_reduce(d1, red, OpAdd()) / cnt);
-  nm.s2 = sqrt(2.0) / (block_reduce(d2, red, OpAdd()) / cnt);
-  if (tid == 0) {
-    double* o = norm + 8 * (long long)p;
-    o[0] = nm.cx1, o[1] = nm.cy1, o[2] = nm.s1, o[3] = nm.cx2, o[4] = nm.cy2, o[5] = nm.s2;
-    o[6] = 0.0, o[7] = 0.0;
-  }
-}
-
-__device__ __forceinline__ Norm load_norm(const double* __restrict__ norm, int p) {
-  const double* o = norm + 8 * (long long)p;
-  return Norm{o[0], o[1], o[2], o[3], o[4], o[5]};
 }
 
 // key of a scored hypothesis: more inliers first, then the lower iteration; 0

@@ -1,6 +1,7 @@
 // ransac_plan.h -- what the host and the kernels of posfeat_ransac_homography
-// (ransac.hip) share: the counter-based sampler, the validation of the set /
-// pair tables and the workspace layout.  Plain C++ with no HIP call, so a
+// (ransac.hip) and posfeat_ransac_fundamental (fundamental.hip) share: the
+// counter-based sampler, the validation of the set / pair tables and the
+// workspace layout.  Plain C++ with no HIP call, so a
 // stand-alone host program can check it (tests/host/ransac_plan_check.cpp);
 // the sampler is also what posfeat_ransac_sample calls.
 //
@@ -61,6 +62,50 @@ PFR_HD inline void sample4(uint64_t seed, int pair, int it, int n, int32_t out[4
   }
 }
 
+// The sampler continued to K draws (4 <= K <= 8): the same base, the same mix,
+// draw k uniform over the n - k indices not drawn yet (n >= K).  The first four
+// draws are sample4's.  The earlier draws are kept ascending in s[]; every
+// index is a compile-time constant once the loops are unrolled.
+template <int K>
+PFR_HD inline void sample_k(uint64_t seed, int pair, int it, int n, int32_t (&out)[K]) {
+  static_assert(K >= 4 && K <= 8, "sample_k draws 4..8 indices");
+  const uint64_t base = mix(mix(seed ^ mix((uint64_t)pair)) ^ (uint64_t)it);
+  int32_t s[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) s[k] = 0;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const uint64_t r = mix(base ^ (uint64_t)k);
+    int32_t j = (int32_t)(((r >> 32) * (uint64_t)(n - k)) >> 32);
+#pragma unroll
+    for (int q = 0; q < k; ++q)
+      if (j >= s[q]) ++j;
+    out[k] = j;
+    int pos = 0;  // the earlier draws below j
+#pragma unroll
+    for (int q = 0; q < k; ++q) pos += s[q] < j ? 1 : 0;
+#pragma unroll
+    for (int q = k; q > 0; --q) s[q] = q < pos ? s[q] : (q == pos ? j : s[q - 1]);
+    s[0] = 0 < pos ? s[0] : j;
+  }
+}
+
+// The slot key of a scored candidate when a sample yields several models
+// (posfeat_ransac_fundamental: the up to three real roots of the 7-point
+// cubic; two bits hold the root index): more
+// inliers first, then the lower iteration, then the lower root index; 0 stays
+// the key of "nothing scored".  it < RMAXITERS, so it * 4 + root fits easily.
+PFR_HD inline unsigned long long slot_key_root(int cnt, int it, int root) {
+  return ((unsigned long long)(unsigned)(cnt + 1) << 32) |
+         (0xffffffffu - (((unsigned)it << 2) | (unsigned)root));
+}
+PFR_HD inline int slot_key_iter(unsigned long long key) {
+  return (int)((0xffffffffu - (unsigned)key) >> 2);
+}
+PFR_HD inline int slot_key_rootidx(unsigned long long key) {
+  return (int)((0xffffffffu - (unsigned)key) & 3u);
+}
+
 struct Pair {  // 32 bytes, read by the device as is
   int32_t a_off, n1;  // pool rows of set s1 (image 1)
   int32_t b_off, n2;  // pool rows of set s2
@@ -106,6 +151,15 @@ inline int build_plan(const int32_t* set_off, int nsets, const int32_t* pairs, i
   pl.slot_off = pl.norm_off + align256((size_t)npairs * 64);
   pl.total_bytes = pl.slot_off + align256((size_t)npairs * pl.nblk * 8) + 256;
   return 0;
+}
+
+// The plan of posfeat_ransac_fundamental: the same tables and the same
+// workspace regions (the slots hold slot_key_root keys); FMINSET is the sample
+// size, below which a pair has no model.
+constexpr int FMINSET = 7;
+inline int build_plan_fundamental(const int32_t* set_off, int nsets, const int32_t* pairs,
+                                  int npairs, int iters, Plan& pl) {
+  return build_plan(set_off, nsets, pairs, npairs, iters, pl);
 }
 
 }  // namespace pfransac_plan

@@ -1,0 +1,130 @@
+"""Geometrically verified matches for a pair list, on the GPU: what the
+reference's Aachen / ETH pipelines do with ``match_features`` followed by
+COLMAP's ``matches_importer`` (evaluations/aachen/reconstruct_pipeline.py
+match_features and geometric_verification), without the COLMAP database.
+
+  verify_pair_list(feature_dir, pairs_file, postfix, matcher="mnn", ratio=0.95,
+                   model="fundamental", chunk=1024, iters=2048, thr=4.0, seed=0,
+                   output=None) -> dict
+
+``pairs_file`` holds one ``name1 name2`` per line (image_pairs_to_match.txt);
+the features of image ``name`` are ``feature_dir/name.postfix`` as extract.py
+wrote them (np.savez: keypoints, descriptors).  Per chunk of at most ``chunk``
+pairs: the images the chunk names are read once and stacked into one pool,
+matchers.match_pairs_device matches the chunk's pairs, then
+geometry.ransac_fundamental_pairs (``model="homography"``:
+ransac_homography_pairs) verifies them on the same PairBatch; counts, matches,
+models, info and masks come back in one copy with one synchronisation.  Pair p
+of a chunk samples as pair p, so the result depends on ``chunk`` through the
+chunking and on nothing else.
+
+The returned dict, also written to ``output`` (np.savez) when given:
+  pairs          [npairs, 2] the image names
+  match_offsets  [npairs + 1] int64: pair p's rows of ``matches``
+  matches        [sum, 2] int32 the inlier matches (index in 1, index in 2)
+  model          [npairs, 3, 3] fp64 F (or H), zeros where none was found
+  info           [npairs, 4] int32 as the RANSAC call gives it
+  n_matches      [npairs] int32 the raw matches before verification
+"""
+import os
+
+import numpy as np
+import torch
+
+from .. import _lib, geometry, matchers
+
+MODELS = {"fundamental": geometry.ransac_fundamental_pairs,
+          "homography": geometry.ransac_homography_pairs}
+
+
+def read_pair_list(pairs_file):
+    """[(name1, name2)] of the non-empty lines"""
+    pairs = []
+    with open(pairs_file) as f:
+        for line in f:
+            parts = line.split()
+            if not parts:
+                continue
+            if len(parts) != 2:
+                raise ValueError("expected 'name1 name2' per line, got %r" % line.rstrip("\n"))
+            pairs.append((parts[0], parts[1]))
+    return pairs
+
+
+def _read_feats(feature_dir, name, postfix):
+    aux = np.load(os.path.join(feature_dir, "%s.%s" % (name, postfix)))
+    return (np.ascontiguousarray(aux["keypoints"][:, :2], dtype=np.float32),
+            np.ascontiguousarray(aux["descriptors"], dtype=np.float32))
+
+
+def _run_chunk(feature_dir, postfix, names, device, matcher, ratio, fit, iters, thr, seed):
+    """names: [(name1, name2)] -> host (counts, matches [sum n1, 2], moff, model, info, mask)"""
+    images = sorted({n for pair in names for n in pair})
+    index = {n: i for i, n in enumerate(images)}
+    feats = [_read_feats(feature_dir, n, postfix) for n in images]
+    pairs = np.asarray([(index[a], index[b]) for a, b in names], dtype=np.int32)
+    npairs = pairs.shape[0]
+    pool, set_off = matchers._pool([d for _, d in feats])
+    if pool.shape[1] != 128:
+        raise NotImplementedError("the matcher kernel is built for 128-d descriptors")
+    kp_pool = torch.from_numpy(np.concatenate([k for k, _ in feats], 0)).to(device)
+    batch = matchers.match_pairs_device(pool, set_off, pairs, matcher, ratio)
+    model, info, inlier = fit(kp_pool, batch, iters=iters, thr=thr, seed=seed)
+    # one synchronisation: everything into one pinned byte buffer
+    parts = [batch.buf.view(torch.uint8), model.view(torch.uint8).view(-1),
+             info.view(torch.uint8).view(-1), inlier]
+    sizes = [int(p.numel()) for p in parts]
+    host = torch.empty(sum(sizes), dtype=torch.uint8, pin_memory=True)
+    at = 0
+    for p, s in zip(parts, sizes):
+        host[at:at + s].copy_(p, non_blocking=True)
+        at += s
+    torch.cuda.current_stream(device).synchronize()
+    h = host.numpy()
+    cuts = np.cumsum([0] + sizes)
+    buf = h[cuts[0]:cuts[1]].view(np.int32)
+    return (buf[:npairs].copy(), buf[npairs:].reshape(-1, 2).copy(), batch.moff,
+            h[cuts[1]:cuts[2]].view(np.float64).reshape(npairs, 3, 3).copy(),
+            h[cuts[2]:cuts[3]].view(np.int32).reshape(npairs, 4).copy(),
+            h[cuts[3]:cuts[4]].astype(bool))
+
+
+def verify_pair_list(feature_dir, pairs_file, postfix, matcher="mnn", ratio=0.95,
+                     model="fundamental", chunk=1024, iters=None, thr=None, seed=0, output=None):
+    if model not in MODELS:
+        raise ValueError("model must be one of %s" % sorted(MODELS))
+    if matcher not in matchers._MODES:
+        raise ValueError("matcher must be one of %s" % sorted(matchers._MODES))
+    if int(chunk) < 1:
+        raise ValueError("chunk must be at least one pair")
+    _lib.require_device()
+    device = torch.device("cuda", torch.cuda.current_device())
+    fit = MODELS[model]
+    # the model's own defaults (iters, thr, seed) where none is given
+    iters = fit.__defaults__[0] if iters is None else int(iters)
+    thr = fit.__defaults__[1] if thr is None else float(thr)
+    names = read_pair_list(pairs_file)
+    kept, offsets, models, infos, raw = [], [0], [], [], []
+    for at in range(0, len(names), int(chunk)):
+        part = names[at:at + int(chunk)]
+        counts, matches, moff, M, info, mask = _run_chunk(feature_dir, postfix, part, device,
+                                                          matcher, ratio, fit, iters, thr, seed)
+        for p in range(len(part)):
+            rows = slice(int(moff[p]), int(moff[p]) + int(counts[p]))
+            kept.append(matches[rows][mask[rows]])
+            offsets.append(offsets[-1] + kept[-1].shape[0])
+        models.append(M)
+        infos.append(info)
+        raw.append(counts)
+    n = len(names)
+    out = dict(
+        pairs=np.asarray(names, dtype=str).reshape(n, 2),
+        match_offsets=np.asarray(offsets, dtype=np.int64),
+        matches=(np.concatenate(kept, 0) if kept else np.zeros((0, 2))).astype(np.int32),
+        model=np.concatenate(models, 0) if models else np.zeros((0, 3, 3)),
+        info=np.concatenate(infos, 0) if infos else np.zeros((0, 4), np.int32),
+        n_matches=np.concatenate(raw, 0) if raw else np.zeros(0, np.int32))
+    if output is not None:
+        with open(output, "wb") as f:
+            np.savez(f, **out)
+    return out

@@ -1,8 +1,8 @@
-"""Robust two-view model fitting on the GPU (ransac.hip): RANSAC homographies
-for every pair of a pair list in three launches, on the matches
-matchers.match_pairs_device left on the device.  The definitions (sampler,
-degeneracy test, minimal solve, score, selection, refit) are in
-include/posfeat_hip.h; no CPU path.
+"""Robust two-view model fitting on the GPU (ransac.hip, fundamental.hip): RANSAC
+homographies or fundamental matrices for every pair of a pair list in three
+launches, on the matches matchers.match_pairs_device left on the device.  The
+definitions (sampler, degeneracy test, minimal solve, score, selection, refit)
+are in include/posfeat_hip.h; no CPU path.
 
   ransac_homography_pairs(kp_pool, batch, iters=1024, thr=3.0, seed=0)
         -> (H [npairs, 3, 3] fp64, info [npairs, 4] int32, inlier [sum n1] uint8)
@@ -11,9 +11,18 @@ include/posfeat_hip.h; no CPU path.
         start at ``batch.moff[p]``.
   find_homography(kp1, kp2, matches, iters=1024, thr=3.0, seed=0)
         one pair, numpy in and out: (H [3, 3], mask [m] bool, info [4]).
-  sample_indices(seed, pair, it, n)
-        the four match indices iteration ``it`` of pair ``pair`` draws from
-        ``n`` matches (host only, needs no device).
+  ransac_fundamental_pairs(kp_pool, batch, iters=2048, thr=4.0, seed=0)
+        -> (F [npairs, 3, 3] fp64, info, inlier), as above; thr is a Sampson
+        distance in pixels and info[p, 3] = refit_kept | root << 8.
+  find_fundamental(kp1, kp2, matches, iters=2048, thr=4.0, seed=0)
+        one pair, numpy in and out: (F [3, 3], mask [m] bool, info [4]).
+  sample_indices(seed, pair, it, n, k=4)
+        the first k match indices (4 for a homography, 7 for a fundamental
+        matrix) iteration ``it`` of pair ``pair`` draws from ``n`` matches (host
+        only, needs no device).
+  solve7(m)
+        the 7-point candidates [c, 3, 3] (c = 0..3) of seven matches m [7, 4] in
+        normalised coordinates (host only, needs no device).
 """
 import ctypes
 
@@ -24,20 +33,38 @@ from . import _lib, matchers
 from ._lib import check, lib, ptr, stream_ptr
 
 
-def sample_indices(seed, pair, it, n):
-    out = np.zeros(4, dtype=np.int32)
-    r = lib().posfeat_ransac_sample(int(seed) & 0xFFFFFFFFFFFFFFFF, int(pair), int(it), int(n),
-                                    ctypes.c_void_p(out.ctypes.data))
+def sample_indices(seed, pair, it, n, k=4):
+    k = int(k)
+    out = np.zeros(max(k, 4), dtype=np.int32)
+    if k == 4:
+        r = lib().posfeat_ransac_sample(int(seed) & 0xFFFFFFFFFFFFFFFF, int(pair), int(it), int(n),
+                                        ctypes.c_void_p(out.ctypes.data))
+    else:
+        r = lib().posfeat_ransac_sample_k(int(seed) & 0xFFFFFFFFFFFFFFFF, int(pair), int(it),
+                                          int(n), k, ctypes.c_void_p(out.ctypes.data))
     if r != 0:
-        raise ValueError("sample_indices needs n >= 4 and non-negative pair and iteration "
-                         "(got n = %d, pair = %d, it = %d)" % (n, pair, it))
-    return out
+        raise ValueError("sample_indices needs 4 <= k <= 8, n >= k and non-negative pair and "
+                         "iteration (got n = %d, pair = %d, it = %d, k = %d)" % (n, pair, it, k))
+    return out[:k]
 
 
-def ransac_homography_pairs(kp_pool, batch, iters=1024, thr=3.0, seed=0):
-    """posfeat_ransac_homography on what ``batch`` (matchers.PairBatch) holds;
-    kp_pool: [N, 2] fp32 device tensor with the row numbering of the descriptor
-    pool the batch was matched from."""
+def solve7(m):
+    """posfeat_fundamental_solve7: m [7, 4] rows (x, y, u, v) in normalised
+    coordinates -> the candidates [c, 3, 3], unit norm, largest entry positive;
+    c = 0 for a rejected sample."""
+    m = np.ascontiguousarray(m, dtype=np.float64)
+    if m.shape != (7, 4):
+        raise ValueError("solve7 takes seven (x, y, u, v) rows")
+    out = np.zeros((3, 3, 3), dtype=np.float64)
+    c = lib().posfeat_fundamental_solve7(ctypes.c_void_p(m.ctypes.data),
+                                         ctypes.c_void_p(out.ctypes.data))
+    if c < 0:
+        raise ValueError("posfeat_fundamental_solve7 failed (%d)" % c)
+    return out[:c]
+
+
+def _ransac_pairs(model, kp_pool, batch, iters, thr, seed):
+    """the one call shape both models share"""
     _lib.require_device(kp_pool)
     if kp_pool.dtype != torch.float32 or kp_pool.dim() != 2 or kp_pool.shape[1] != 2:
         raise ValueError("kp_pool must be a [N, 2] float32 tensor")
@@ -47,26 +74,36 @@ def ransac_homography_pairs(kp_pool, batch, iters=1024, thr=3.0, seed=0):
     if kp_pool.shape[0] < int(set_off[-1]):
         raise ValueError("kp_pool has fewer rows than the sets of the batch")
     so, pp = ctypes.c_void_p(set_off.ctypes.data), ctypes.c_void_p(pairs.ctypes.data)
-    need = lib().posfeat_ransac_homography_workspace(so, nsets, pp, npairs, int(iters))
+    need = getattr(lib(), "posfeat_ransac_%s_workspace" % model)(so, nsets, pp, npairs, int(iters))
     if need == 0:
         raise ValueError("invalid pair tables, or iters outside 1..65536")
     dev = kp_pool.device
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    H = torch.empty(npairs, 3, 3, dtype=torch.float64, device=dev)
+    M = torch.empty(npairs, 3, 3, dtype=torch.float64, device=dev)
     info = torch.empty(npairs, 4, dtype=torch.int32, device=dev)
     inlier = torch.empty(int(batch.moff[-1]), dtype=torch.uint8, device=dev)
-    check(lib().posfeat_ransac_homography(
+    check(getattr(lib(), "posfeat_ransac_%s" % model)(
         ptr(kp_pool), so, nsets, pp, npairs, ptr(batch.matches), ptr(batch.counts), int(iters),
-        float(thr), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(H), ptr(info), ptr(inlier), ptr(ws), need,
+        float(thr), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(M), ptr(info), ptr(inlier), ptr(ws), need,
         stream_ptr(dev)))
-    return H, info, inlier
+    return M, info, inlier
 
 
-def find_homography(kp1, kp2, matches, iters=1024, thr=3.0, seed=0):
-    """One pair through the same call: kp1 [n1, >=2], kp2 [n2, >=2] keypoints
-    (x, y), matches [m, 2] (index in 1, index in 2), m <= n1.  Returns (H [3, 3]
-    fp64 with Frobenius norm 1, mask [m] bool, info [4] int32); H is all zeros
-    and info[0] = 1 when no model was found."""
+def ransac_homography_pairs(kp_pool, batch, iters=1024, thr=3.0, seed=0):
+    """posfeat_ransac_homography on what ``batch`` (matchers.PairBatch) holds;
+    kp_pool: [N, 2] fp32 device tensor with the row numbering of the descriptor
+    pool the batch was matched from."""
+    return _ransac_pairs("homography", kp_pool, batch, iters, thr, seed)
+
+
+def ransac_fundamental_pairs(kp_pool, batch, iters=2048, thr=4.0, seed=0):
+    """posfeat_ransac_fundamental on what ``batch`` (matchers.PairBatch) holds;
+    the arguments of ransac_homography_pairs.  thr = 4 px is COLMAP's two-view
+    max_error default."""
+    return _ransac_pairs("fundamental", kp_pool, batch, iters, thr, seed)
+
+
+def _find(model, kp1, kp2, matches, iters, thr, seed):
     _lib.require_device()
     dev = torch.device("cuda", torch.cuda.current_device())
     kp1 = np.ascontiguousarray(np.asarray(kp1)[:, :2], dtype=np.float32)
@@ -84,5 +121,19 @@ def find_homography(kp1, kp2, matches, iters=1024, thr=3.0, seed=0):
     buf = torch.from_numpy(np.concatenate([[m], rows.reshape(-1)]).astype(np.int32)).to(dev)
     batch = matchers.PairBatch(None, set_off, pairs, np.asarray([0, n1]), buf)
     kp_pool = torch.from_numpy(np.concatenate([kp1, kp2], 0)).to(dev)
-    H, info, inlier = ransac_homography_pairs(kp_pool, batch, iters, thr, seed)
-    return H[0].cpu().numpy(), inlier[:m].cpu().numpy().astype(bool), info[0].cpu().numpy()
+    M, info, inlier = _ransac_pairs(model, kp_pool, batch, iters, thr, seed)
+    return M[0].cpu().numpy(), inlier[:m].cpu().numpy().astype(bool), info[0].cpu().numpy()
+
+
+def find_homography(kp1, kp2, matches, iters=1024, thr=3.0, seed=0):
+    """One pair through the same call: kp1 [n1, >=2], kp2 [n2, >=2] keypoints
+    (x, y), matches [m, 2] (index in 1, index in 2), m <= n1.  Returns (H [3, 3]
+    fp64 with Frobenius norm 1, mask [m] bool, info [4] int32); H is all zeros
+    and info[0] = 1 when no model was found."""
+    return _find("homography", kp1, kp2, matches, iters, thr, seed)
+
+
+def find_fundamental(kp1, kp2, matches, iters=2048, thr=4.0, seed=0):
+    """find_homography's counterpart for a fundamental matrix: (F [3, 3] fp64
+    with Frobenius norm 1, mask [m] bool, info [4] int32)."""
+    return _find("fundamental", kp1, kp2, matches, iters, thr, seed)
