@@ -854,6 +854,109 @@ int posfeat_ransac_fundamental(const float *kp, const int32_t *set_off, int nset
                                double *F, int32_t *info, uint8_t *inlier, void *ws,
                                size_t ws_bytes, void *stream);
 
+/* Feature tracks and one robustly triangulated 3-D point per track from
+ * verified matches and known cameras: what the reference's Aachen pipeline
+ * asks of `colmap point_triangulator` after geometric_verification
+ * (evaluations/aachen/reconstruct_pipeline.py).  All in fp64.
+ * set_off (nsets + 1 entries, set_off[0] = 0, not decreasing) is a HOST table;
+ * every other pointer is a device pointer.  N = set_off[nsets] pool rows; row r
+ * belongs to the set s with set_off[s] <= r < set_off[s + 1]; a set is an image.
+ *   kp     [N][2] fp32       pixel (x, y), used as given
+ *   cams   [nsets][8] fp64   (fx, fy, cx, cy, k1, 0, 0, 0)
+ *   poses  [nsets][12] fp64  [R | t] row-major, world to camera, x_cam = R X + t
+ *                            (COLMAP's convention); the centre is C = -R^T t
+ *   edges  [nedges][2] int32 global pool rows
+ *   camera       once per row.  Undistortion: xd = (x - cx) / fx, yd = (y - cy) /
+ *                fy, rd = hypot(xd, yd); for k1 = 0 or rd = 0 the undistorted
+ *                point (xu, yu) is (xd, yd); otherwise ru starts at rd and takes
+ *                exactly 8 Newton steps ru <- ru - g / g' on g(ru) = ru (1 + k1
+ *                ru^2) - rd, g' = 1 + 3 k1 ru^2, a step whose g' is not a
+ *                positive finite number skipped, and (xu, yu) = (ru / rd) (xd,
+ *                yd).  Projection of X: (xc, yc, z) = R X + t, xn = xc / z, yn =
+ *                yc / z, f = 1 + k1 (xn^2 + yn^2), pixel = (fx f xn + cx, fy f yn
+ *                + cy).  The reprojection error is the pixel distance to (x, y);
+ *                an observation is an inlier of X iff z > 0 and the squared
+ *                error is finite and <= thr^2;
+ *   tracks       an edge is ignored, before any memory is touched through it,
+ *                when an end lies outside [0, N), both ends are in one set, or
+ *                both ends are one row.  Duplicate and reversed edges are
+ *                harmless.  root(r) = the smallest row of r's connected
+ *                component.  A component of 2..max_track rows is a track;
+ *                larger ones are dropped (and counted).  Tracks are numbered in
+ *                ascending root order, members listed in ascending row order;
+ *                nothing depends on the order of `edges`;
+ *   DLT          each observation, in a given order, contributes the two
+ *                4-vectors a = xu P3 - P1 and b = yu P3 - P2 (Pi the rows of [R |
+ *                t]); N4 = sum (a a^T + b b^T), every entry accumulated in that
+ *                order (first a's product, then b's); its eigenvectors by the
+ *                cyclic Jacobi of posfeat_ransac_fundamental's refit (the same
+ *                visiting order, rotation formulas, stopping rule, at most 16
+ *                sweeps); v = the eigenvector of the lowest diagonal entry (the
+ *                first on a tie).  Rejected when |v4| <= 1e-12 max |vi| or
+ *                anything is not finite; else X = (v1, v2, v3) / v4;
+ *   hypotheses   a track with members 0..m-1 (ascending rows), root row rho, H
+ *                = m (m - 1) / 2.  H <= iters: hypothesis h is the h-th pair (i <
+ *                j) in lexicographic order, h = 0..H-1.  Otherwise (then m >= 5)
+ *                hypothesis h = 0..iters-1 takes (i, j) = the first two draws of
+ *                posfeat_ransac_sample(seed, rho, h, m), as drawn, not sorted.  X
+ *                = the DLT of observations i, j in that order.  Rejected when
+ *                the DLT rejects, z <= 0 in view i or j, or the angle at X
+ *                between X - Ci and X - Cj is below min_angle_deg: with d = (X -
+ *                Ci) . (X - Cj) and the two lengths, the test passes iff both
+ *                lengths are > 0 and d / (|X - Ci| |X - Cj|) < cos(min_angle_deg)
+ *                (two observations in one image never survive);
+ *   score        the number of members that are inliers of X;
+ *   selection    most inliers, ties to the lowest h; rejected hypotheses never
+ *                win;
+ *   refit        the DLT over the winner's inliers in member order; kept iff it
+ *                is accepted, its own inlier count is >= the winner's, z > 0 in
+ *                the winning pair's two views and the winning pair's angle at
+ *                the new X passes.  When kept, the flags are the refit's.
+ * Outputs (device), Tmax = min(nedges, N / 2), Mmax = min(2 nedges, N):
+ *   points [Tmax][3], err [Tmax]: the point and the mean reprojection error in
+ *     pixels of its final inliers (their sum in member order over their number;
+ *     0 without an inlier);
+ *   tinfo [Tmax][4] = {status, n_inliers, best_h, refit_kept}; status 1 (every
+ *     hypothesis rejected): point 0, err 0, {1, 0, -1, 0}, flags 0;
+ *   track_off [Tmax + 1], track_rows [Mmax], obs_inlier [Mmax] (uint8, parallel
+ *     to track_rows): track t has the members track_rows[track_off[t] ..
+ *     track_off[t + 1]);
+ *   point_of_row [N]: the track id where the row is a final inlier of a status-0
+ *     track, else -1;
+ *   counts [8] = {T, members, points with status 0, inlier observations, dropped
+ *     oversized components, ignored edges, 0, 0}.
+ * Entries past T / the member count are not written.  Every output buffer must
+ * hold at least one element.
+ * Returns, before any device work: POSFEAT_E_INVALID for a null pointer (an
+ * input without elements may be null: kp for N = 0, cams and poses for nsets =
+ * 0, edges for nedges = 0), a null set_off, nsets < 0, set_off[0] != 0, a
+ * decreasing set_off, iters outside 8..1024, max_track outside 2..1024, a
+ * non-finite or non-positive thr, min_angle_deg outside [0, 90), a negative
+ * nedges, ws not 256-B aligned, points or err not 8-B aligned;
+ * POSFEAT_E_WORKSPACE for ws_bytes below
+ * posfeat_triangulate_workspace (0 for invalid arguments).  nedges = 0 and N = 0
+ * are valid and give counts = 0.  Camera and pose values are data: non-finite
+ * entries only make observations fail the inlier test.
+ * Nine launches (and one copy of set_off) whatever N, nedges and T;
+ * stream-ordered, never synchronises the host; NOT graph-capturable (set_off is
+ * copied from pageable host memory).  Deterministic: the same inputs give the
+ * same bits, and the result for a track (its point, err, info, members, flags)
+ * depends only on its own component's rows, their cameras, seed, iters, thr
+ * and min_angle_deg.
+ * posfeat_triangulate_dlt is host only (no device, no launch) and compiles the
+ * text the kernels compile: obs [n][14] = (xu, yu, the 12 pose entries), n >= 1,
+ * to X [3]; returns 0, 1 for a rejected system (X = 0), POSFEAT_E_INVALID for a
+ * null pointer or n < 1. */
+size_t posfeat_triangulate_workspace(const int32_t *set_off, int nsets, long long nedges,
+                                     int max_track);
+int posfeat_triangulate(const float *kp, const int32_t *set_off, int nsets, const double *cams,
+                        const double *poses, const int32_t *edges, long long nedges, int iters,
+                        double thr, double min_angle_deg, int max_track, uint64_t seed,
+                        double *points, double *err, int32_t *tinfo, int32_t *track_off,
+                        int32_t *track_rows, uint8_t *obs_inlier, int32_t *point_of_row,
+                        int32_t *counts, void *ws, size_t ws_bytes, void *stream);
+int posfeat_triangulate_dlt(const double *obs, int n, double *X);
+
 #ifdef __cplusplus
 }
 #endif

@@ -231,6 +231,11 @@ SIGNATURES = {
                                           c_void_p, c_int, ctypes.c_double, ctypes.c_uint64,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                           c_void_p]),
+    "posfeat_triangulate_workspace": (c_size_t, [c_void_p, c_int, c_ll, c_int]),
+    "posfeat_triangulate": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_ll,
+                                    c_int, ctypes.c_double, ctypes.c_double, c_int,
+                                    ctypes.c_uint64] + [c_void_p] * 9 + [c_size_t, c_void_p]),
+    "posfeat_triangulate_dlt": (c_int, [c_void_p, c_int, c_void_p]),
 }
 
 

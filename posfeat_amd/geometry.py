@@ -1,8 +1,9 @@
 """Robust two-view model fitting on the GPU (ransac.hip, fundamental.hip): RANSAC
 homographies or fundamental matrices for every pair of a pair list in three
-launches, on the matches matchers.match_pairs_device left on the device.  The
-definitions (sampler, degeneracy test, minimal solve, score, selection, refit)
-are in include/posfeat_hip.h; no CPU path.
+launches, on the matches matchers.match_pairs_device left on the device; and
+tracks with one triangulated point each from the verified matches
+(triangulate.hip).  The definitions (sampler, degeneracy test, minimal solve,
+score, selection, refit) are in include/posfeat_hip.h; no CPU path.
 
   ransac_homography_pairs(kp_pool, batch, iters=1024, thr=3.0, seed=0)
         -> (H [npairs, 3, 3] fp64, info [npairs, 4] int32, inlier [sum n1] uint8)
@@ -23,6 +24,17 @@ are in include/posfeat_hip.h; no CPU path.
   solve7(m)
         the 7-point candidates [c, 3, 3] (c = 0..3) of seven matches m [7, 4] in
         normalised coordinates (host only, needs no device).
+  triangulate_tracks(kp_pool, set_off, cams, poses, edges, iters=64, thr=4.0,
+                     min_angle=1.5, max_track=256, seed=0) -> TrackResult
+        posfeat_triangulate (triangulate.hip): feature tracks from match edges
+        and one RANSAC-triangulated point per track, device tensors in and out,
+        nothing read back; ``.host()`` brings everything back in one copy.
+  track_edges(batch, inlier)
+        the global-row edges [sum n1, 2] int32 of a PairBatch and its RANSAC
+        mask (device, torch ops only; -1 rows where there is no inlier match).
+  triangulate_dlt(obs)
+        the DLT of obs [n, 14] = (xu, yu, pose) rows (host only, needs no
+        device): X [3], or None for a rejected system.
 """
 import ctypes
 
@@ -137,3 +149,132 @@ def find_fundamental(kp1, kp2, matches, iters=2048, thr=4.0, seed=0):
     """find_homography's counterpart for a fundamental matrix: (F [3, 3] fp64
     with Frobenius norm 1, mask [m] bool, info [4] int32)."""
     return _find("fundamental", kp1, kp2, matches, iters, thr, seed)
+
+
+def triangulate_dlt(obs):
+    """posfeat_triangulate_dlt: obs [n, 14] rows (xu, yu, the 12 entries of [R |
+    t] row-major) -> X [3], or None when the system is rejected."""
+    obs = np.ascontiguousarray(obs, dtype=np.float64)
+    if obs.ndim != 2 or obs.shape[1] != 14 or obs.shape[0] < 1:
+        raise ValueError("triangulate_dlt takes [n >= 1, 14] rows (xu, yu, pose)")
+    X = np.zeros(3, dtype=np.float64)
+    r = lib().posfeat_triangulate_dlt(ctypes.c_void_p(obs.ctypes.data), obs.shape[0],
+                                      ctypes.c_void_p(X.ctypes.data))
+    if r < 0:
+        raise ValueError("posfeat_triangulate_dlt failed (%d)" % r)
+    return X if r == 0 else None
+
+
+class TrackResult:
+    """What one posfeat_triangulate call left on the device, cut to the worst
+    case (Tmax = min(nedges, N // 2) tracks, Mmax = min(2 nedges, N) members):
+    ``points`` [Tmax, 3] fp64, ``err`` [Tmax] fp64, ``tinfo`` [Tmax, 4] int32,
+    ``track_off`` [Tmax + 1] int32, ``track_rows`` [Mmax] int32, ``obs_inlier``
+    [Mmax] uint8, ``point_of_row`` [N] int32, ``counts`` [8] int32.  Rows past
+    counts[0] tracks / counts[1] members are not written."""
+
+    FIELDS = ("points", "err", "tinfo", "track_off", "track_rows", "obs_inlier", "point_of_row",
+              "counts")
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw[k])
+
+    def host(self):
+        """Everything on the host as numpy arrays trimmed by ``counts``: one
+        pinned copy, one synchronisation."""
+        parts = [getattr(self, k) for k in self.FIELDS]
+        flat = [p.reshape(-1).view(torch.uint8) for p in parts]
+        sizes = [int(f.numel()) for f in flat]
+        host = torch.empty(sum(sizes), dtype=torch.uint8, pin_memory=True)
+        at = 0
+        for f, n in zip(flat, sizes):
+            host[at:at + n].copy_(f, non_blocking=True)
+            at += n
+        torch.cuda.current_stream(self.counts.device).synchronize()
+        h, cuts = host.numpy(), np.cumsum([0] + sizes)
+        raw = {k: h[cuts[i]:cuts[i + 1]] for i, k in enumerate(self.FIELDS)}
+        counts = raw["counts"].view(np.int32).copy()
+        T, M = int(counts[0]), int(counts[1])
+        return dict(
+            points=raw["points"].view(np.float64).reshape(-1, 3)[:T].copy(),
+            err=raw["err"].view(np.float64)[:T].copy(),
+            tinfo=raw["tinfo"].view(np.int32).reshape(-1, 4)[:T].copy(),
+            track_off=raw["track_off"].view(np.int32)[:T + 1].copy(),
+            track_rows=raw["track_rows"].view(np.int32)[:M].copy(),
+            obs_inlier=raw["obs_inlier"][:M].copy(),
+            point_of_row=raw["point_of_row"].view(np.int32)[:self.point_of_row.shape[0]].copy(),
+            counts=counts)
+
+
+def triangulate_tracks(kp_pool, set_off, cams, poses, edges, iters=64, thr=4.0, min_angle=1.5,
+                       max_track=256, seed=0):
+    """posfeat_triangulate: kp_pool [N, 2] fp32, cams [nsets, 8] fp64, poses
+    [nsets, 12] fp64 (or [nsets, 3, 4]), edges [E, 2] int32 device tensors;
+    set_off [nsets + 1] a host int32 table.  thr = 4 px and min_angle = 1.5
+    degrees are COLMAP's filter_max_reproj_error and filter_min_tri_angle."""
+    _lib.require_device(kp_pool)
+    dev = kp_pool.device
+    set_off = np.ascontiguousarray(set_off, dtype=np.int32)
+    nsets = set_off.shape[0] - 1
+    if kp_pool.dtype != torch.float32 or kp_pool.dim() != 2 or kp_pool.shape[1] != 2:
+        raise ValueError("kp_pool must be a [N, 2] float32 tensor")
+    if nsets < 0 or kp_pool.shape[0] != int(set_off[-1]):
+        raise ValueError("kp_pool must have set_off[-1] rows")
+    poses = poses.reshape(-1, 12)
+    for name, t, shape, dt in (("cams", cams, (nsets, 8), torch.float64),
+                               ("poses", poses, (nsets, 12), torch.float64)):
+        if t.device != dev or t.dtype != dt or tuple(t.shape) != shape:
+            raise ValueError("%s must be a %s %s tensor on the keypoints' device" % (name, shape, dt))
+    if edges.device != dev or edges.dtype != torch.int32 or edges.dim() != 2 or edges.shape[1] != 2:
+        raise ValueError("edges must be a [E, 2] int32 tensor on the keypoints' device")
+    kp_pool, cams, poses, edges = (t.contiguous() for t in (kp_pool, cams, poses, edges))
+    N, E = int(set_off[-1]), int(edges.shape[0])
+    so = ctypes.c_void_p(set_off.ctypes.data)
+    need = lib().posfeat_triangulate_workspace(so, nsets, E, int(max_track))
+    if need == 0:
+        raise ValueError("invalid set table, or max_track outside 2..1024")
+    tmax, mmax = min(E, N // 2), min(2 * E, N)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    out = TrackResult(
+        points=torch.empty(max(tmax, 1), 3, dtype=torch.float64, device=dev),
+        err=torch.empty(max(tmax, 1), dtype=torch.float64, device=dev),
+        tinfo=torch.empty(max(tmax, 1), 4, dtype=torch.int32, device=dev),
+        track_off=torch.empty(tmax + 1, dtype=torch.int32, device=dev),
+        track_rows=torch.empty(max(mmax, 1), dtype=torch.int32, device=dev),
+        obs_inlier=torch.empty(max(mmax, 1), dtype=torch.uint8, device=dev),
+        point_of_row=torch.empty(max(N, 1), dtype=torch.int32, device=dev),
+        counts=torch.empty(8, dtype=torch.int32, device=dev))
+    check(lib().posfeat_triangulate(
+        ptr(kp_pool), so, nsets, ptr(cams), ptr(poses), ptr(edges), E, int(iters), float(thr),
+        float(min_angle), int(max_track), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(out.points),
+        ptr(out.err), ptr(out.tinfo), ptr(out.track_off), ptr(out.track_rows), ptr(out.obs_inlier),
+        ptr(out.point_of_row), ptr(out.counts), ptr(ws), need, stream_ptr(dev)))
+    out.point_of_row = out.point_of_row[:N]
+    return out
+
+
+def track_edges(batch, inlier):
+    """The match graph of a PairBatch: row moff[p] + i of the result holds the
+    global pool rows (set_off[s1] + a, set_off[s2] + b) of match i of pair p
+    where i < counts[p] and ``inlier`` (the RANSAC mask, [sum n1] uint8 or
+    bool) is set, else (-1, -1), which posfeat_triangulate ignores.  Torch ops
+    on the device only; the per-row pair tables come from the host tables."""
+    set_off = np.asarray(batch.set_off, dtype=np.int64)
+    pairs = np.asarray(batch.pairs, dtype=np.int64).reshape(-1, 2)
+    moff = np.asarray(batch.moff, dtype=np.int64)
+    dev = batch.matches.device
+    n1 = np.diff(moff)
+    pair_of = np.repeat(np.arange(pairs.shape[0]), n1)
+    local = np.arange(int(moff[-1])) - moff[:-1][pair_of]
+    tab = np.stack([pair_of, local, set_off[pairs[pair_of, 0]], set_off[pairs[pair_of, 1]],
+                    set_off[pairs[pair_of, 1] + 1] - set_off[pairs[pair_of, 1]], n1[pair_of]], 1)
+    tab = torch.from_numpy(np.ascontiguousarray(tab)).to(dev)
+    if tab.shape[0] == 0:
+        return torch.empty(0, 2, dtype=torch.int32, device=dev)
+    m = batch.matches.to(torch.int64)
+    a, b = m[:, 0], m[:, 1]
+    ok = ((tab[:, 1] < batch.counts.to(torch.int64)[tab[:, 0]]) & (inlier.reshape(-1) != 0) &
+          (a >= 0) & (a < tab[:, 5]) & (b >= 0) & (b < tab[:, 4]))
+    e = torch.stack([tab[:, 2] + a, tab[:, 3] + b], 1)
+    return torch.where(ok[:, None], e, torch.full_like(e, -1)).to(torch.int32)

@@ -1,0 +1,39 @@
+"""A sparse model from verified matches and known database poses (the
+reference's ``colmap point_triangulator`` step of
+evaluations/aachen/reconstruct_pipeline.py, on the GPU and without COLMAP):
+``python triangulate_pairs.py --verified verified.npz --features DIR --postfix NAME
+--intrinsics database_intrinsics.txt --nvm MODEL.nvm --out MODEL_DIR [--thr T]
+[--min_angle DEG] [--iters N] [--max_track M] [--seed S]``.
+verified.npz is what verify_pairs.py wrote; DIR holds ``<image name>.<postfix>``
+as extract.py wrote them.  Writes COLMAP's text model (cameras.txt, images.txt,
+points3D.txt) to MODEL_DIR and prints the summary
+posfeat_amd.evaluation.reconstruction.triangulate_pair_list describes."""
+import argparse
+
+from posfeat_amd.evaluation import reconstruction
+
+if __name__ == "__main__":
+    parser = argparse.ArgumentParser()
+    parser.add_argument("--verified", type=str, required=True)
+    parser.add_argument("--features", type=str, required=True)
+    parser.add_argument("--postfix", type=str, required=True)
+    parser.add_argument("--intrinsics", type=str, required=True)
+    parser.add_argument("--nvm", type=str, required=True)
+    parser.add_argument("--out", type=str, required=True)
+    parser.add_argument("--thr", type=float, default=4.0)
+    parser.add_argument("--min_angle", type=float, default=1.5)
+    parser.add_argument("--iters", type=int, default=64)
+    parser.add_argument("--max_track", type=int, default=256)
+    parser.add_argument("--seed", type=int, default=0)
+    args = parser.parse_args()
+    res = reconstruction.triangulate_pair_list(
+        args.verified, args.features, args.postfix, args.intrinsics, args.nvm, thr=args.thr,
+        min_angle=args.min_angle, iters=args.iters, max_track=args.max_track, seed=args.seed)
+    reconstruction.write_model(res, args.out)
+    s, c = res["summary"], res["counts"]
+    print("# Images: {:d}, skipped pairs: {:d}, tracks: {:d} (dropped {:d}, ignored edges {:d})".format(
+        len(res["images"]), res["skipped_pairs"], int(c[0]), int(c[4]), int(c[5])))
+    print("# Points: {:d}\n# Observations: {:d}\n# Mean track length: {:.6f}\n"
+          "# Mean reprojection error: {:.6f}px".format(
+              s["points"], s["observations"], s["mean_track_length"],
+              s["mean_reprojection_error"]))
