@@ -957,6 +957,132 @@ int posfeat_triangulate(const float *kp, const int32_t *set_off, int nsets, cons
                         int32_t *counts, void *ws, size_t ws_bytes, void *stream);
 int posfeat_triangulate_dlt(const double *obs, int n, double *X);
 
+/* RANSAC absolute poses for every query of a list from 2D-3D correspondences:
+ * what the reference's Aachen pipeline asks of `colmap image_registrator`
+ * after the sparse model is built (evaluations/aachen/reconstruct_pipeline.py
+ * register_queries).  All in fp64.  q_off (nq + 1 entries, q_off[0] = 0, not
+ * decreasing; C = q_off[nq] correspondences) is a HOST table; every other
+ * pointer is a device pointer.
+ *   kp     [nkp][2] fp32      the queries' keypoint pool, pixel (x, y)
+ *   cams   [nq][8] fp64       posfeat_triangulate's camera row, one per query
+ *   points [npoints][3] fp64  world points (posfeat_triangulate's `points`, as
+ *                             left on the device)
+ *   corr   [C][2] int32       (pool row, point index); query q owns rows q_off[q]
+ *                             .. q_off[q + 1], numbered 0 .. n - 1 below
+ *   rows         a correspondence is invalid when its pool row is outside [0,
+ *                nkp), its point index outside [0, npoints), or its pixel,
+ *                undistorted point or world point is not finite.  An invalid
+ *                correspondence is never an inlier and rejects every sample
+ *                that draws it; nothing is read through its indices.  The
+ *                undistorted normalised point (xu, yu) is posfeat_triangulate's
+ *                `camera` undistortion (exactly 8 Newton steps);
+ *   sample       iteration it = 0 .. iters - 1 of query q takes the first three
+ *                draws of posfeat_ransac_sample(seed, q, it, n), as drawn: the
+ *                correspondences 1, 2, 3 with world points P1, P2, P3 and unit
+ *                bearings fi = (xu, yu, 1) / |(xu, yu, 1)|.  A query needs n >=
+ *                4.  Rejected when a drawn correspondence is invalid; when |(P2
+ *                - P1) x (P3 - P1)| <= 1e-6 |P2 - P1| |P3 - P1| (collinear or
+ *                coincident points; a NaN rejects); or when two bearings have a
+ *                cosine >= 1 - 1e-12;
+ *   quartic      Grunert's: a2 = |P2 - P3|^2, b2 = |P1 - P3|^2, c2 = |P1 - P2|^2,
+ *                ca = f2 . f3, cb = f1 . f3, cg = f1 . f2, k = (a2 - c2) / b2, m =
+ *                (a2 + c2) / b2; with the depths s2 = u s1, s3 = v s1 the ratio v
+ *                solves A4 v^4 + A3 v^3 + A2 v^2 + A1 v + A0 = 0,
+ *                  A4 = (k - 1)^2 - 4 (c2 / b2) ca^2
+ *                  A3 = 4 [k (1 - k) cb - (1 - m) ca cg + 2 (c2 / b2) ca^2 cb]
+ *                  A2 = 2 [k^2 - 1 + 2 k^2 cb^2 + 2 ((b2 - c2) / b2) ca^2
+ *                          - 4 m ca cb cg + 2 ((b2 - a2) / b2) cg^2]
+ *                  A1 = 4 [-k (1 + k) cb + 2 (a2 / b2) cg^2 cb - (1 - m) ca cg]
+ *                  A0 = (1 + k)^2 - 4 (a2 / b2) cg^2;
+ *   roots        in closed form, no iteration with a data-dependent trip count.
+ *                With cm = max |Ak|: |A4| <= 1e-12 cm: the cubic A3 v^3 + ... + A0
+ *                by posfeat_ransac_fundamental's `roots` (closed form, two
+ *                Newton steps, its own fall-back to the quadratic and the linear
+ *                case).  Otherwise Ferrari: when |A0| > |A4| the coefficients
+ *                are reversed first (the quartic in 1 / v; its roots are inverted
+ *                at the end and a root 0 is dropped), so that a root far out
+ *                does not swamp the others.  The monic quartic y^4 + a y^3 + b
+ *                y^2 + c y + d is depressed by y -> y - a / 4 to y^4 + p y^2 + q y
+ *                + r, p = b - 3 a^2 / 8, q = c - a b / 2 + a^3 / 8, r = d - a c / 4 +
+ *                a^2 b / 16 - 3 a^4 / 256; m = the largest real root of the
+ *                resolvent 8 m^3 + 8 p m^2 + (2 p^2 - 8 r) m - q^2 by the same
+ *                `roots`.  For a finite m > 0, with s = sqrt(2 m), h = p / 2 + m,
+ *                w = q / (2 s), the quartic is (y^2 + s y + h - w)(y^2 - s y + h +
+ *                w); a factor y^2 + B y + C with B^2 - 4 C >= 0 gives t = -(B +
+ *                sign(B) sqrt(B^2 - 4 C)) / 2 and C / t.  Otherwise the
+ *                biquadratic: z^2 + p z + r the same way (second root r / t, 0
+ *                for t = 0; none for a negative discriminant), every z >= 0
+ *                giving +-sqrt(z).  Every root then takes two Newton steps on
+ *                the quartic as given, A4 v^4 + ... + A0 (a step with a zero
+ *                derivative or a non-finite result is skipped).  The roots are
+ *                sorted ascending and a root within 1e-9 max(1, |v|) of the
+ *                last root kept is dropped (roots that close count once);
+ *   candidates   a root v is a candidate iff v > 0, u = [(k - 1) v^2 - 2 k cb v
+ *                + 1 + k] / (2 (cg - v ca)) is finite and > 0, s1 = sqrt(b2 / (1
+ *                + v^2 - 2 v cb)) is finite and > 0, and its pose is finite.
+ *                With the camera points Qi = si fi, the triad of three points
+ *                (A, B, C) is e1 = (B - A) / |B - A|, e3 = e1 x (C - A)
+ *                normalised, e2 = e3 x e1, T = [e1 e2 e3] (columns): R = T(Q1,
+ *                Q2, Q3) T(P1, P2, P3)^T, t = Q1 - R P1.  At most four
+ *                candidates, numbered r = 0 .. 3 in ascending v;
+ *   score        the number of correspondences that are inliers of [R | t]:
+ *                with (xc, yc, z) = R X + t, z > 0 and the squared pixel
+ *                reprojection error (posfeat_triangulate's `camera`
+ *                projection, distortion included) finite and <= thr^2.  It is
+ *                evaluated without the division: with g = z^2 + k1 (xc^2 +
+ *                yc^2), xd = (x - cx) / fx, yd = (y - cy) / fy, the error times
+ *                z^3 is (fx (xc g - xd z^3), fy (yc g - yd z^3)), compared with
+ *                thr^2 z^6 (which must be finite);
+ *   selection    most inliers, ties to the lowest iteration, then to the lowest
+ *                candidate number; rejected samples never win;
+ *   refit        Gauss-Newton on the pixel reprojection error over the winner's
+ *                inliers (the set stays fixed), attempted iff there are at
+ *                least 4.  The unknowns delta = (omega, tau) perturb a camera
+ *                point as Xc + omega x Xc + tau.  Per inlier the residual r =
+ *                projection - (x, y) and its 2 x 6 Jacobian J = (d pixel / d
+ *                Xc) [-[Xc]x | I]; N = sum J^T J (upper triangle), g = sum J^T
+ *                r and the cost sum |r|^2 are accumulated in a fixed order.  N
+ *                delta = -g by Gaussian elimination with partial pivoting (the
+ *                first largest entry of the column); a pivot below 1e-12 times
+ *                the largest entry of its column of N, or not positive, or a
+ *                non-finite delta, stops the refit.  The step R <- exp(omega) R,
+ *                t <- exp(omega) t + tau (Rodrigues: exp = I + (sin th / th) K +
+ *                (2 sin^2(th / 2) / th^2) K^2, K = [omega]x, th = |omega|; I + K
+ *                + K^2 / 2 for th = 0) is taken iff at the new pose every
+ *                inlier has z > 0 and a finite residual and the cost is lower;
+ *                a refused step stops the refit.  At most 10 steps; after a
+ *                step with max |delta_i| <= 1e-12 it stops too.  The refit's
+ *                pose is kept iff it is finite and its own inlier count (over
+ *                all correspondences) is >= the winner's; the mask is then the
+ *                refit's.
+ * Outputs (device): poses [nq][12] = [R | t] row-major, world to camera; info
+ * [nq][4] = {status, n_inliers, best_iter, refit_kept | root << 8} with root the
+ * winning candidate's number; inlier [C] uint8 parallel to corr.  status 1
+ * (fewer than 4 correspondences, or every sample rejected): pose 0, info {1, 0,
+ * -1, 0}, mask 0.
+ * Returns, before any device work: POSFEAT_E_INVALID for a null pointer, nq < 0,
+ * q_off[0] != 0, a decreasing q_off, nkp or npoints < 0, iters outside 1..65536,
+ * a non-finite or non-positive thr, ws not 256-B aligned, poses, points or cams
+ * not 8-B aligned, info or corr not 4-B aligned; POSFEAT_E_WORKSPACE for
+ * ws_bytes below posfeat_ransac_pose_workspace (0 for an invalid table or
+ * iteration count).  nq = 0 is valid and does nothing.
+ * Three launches (and one copy of q_off) whatever nq; stream-ordered, never
+ * synchronises the host; NOT graph-capturable (q_off is copied from pageable
+ * host memory).  Deterministic: the same inputs give the same bits, and the
+ * result for a query index depends only on that index, its own correspondences
+ * and camera, seed, iters and thr.
+ * posfeat_pose_solve3 is host only (no device, no launch) and compiles the text
+ * the kernels compile, with the host's acos / cos / cbrt: it runs `sample`'s
+ * rejections to `candidates` on m [3][5] = (xu, yu, X, Y, Z) rows, writes the
+ * candidate poses to poses [<= 4][12] and returns their number: 0 for a rejected
+ * sample, POSFEAT_E_INVALID for a null pointer. */
+size_t posfeat_ransac_pose_workspace(const int32_t *q_off, int nq, int iters);
+int posfeat_ransac_pose(const float *kp, long long nkp, const double *cams, const double *points,
+                        long long npoints, const int32_t *corr, const int32_t *q_off, int nq,
+                        int iters, double thr, uint64_t seed, double *poses, int32_t *info,
+                        uint8_t *inlier, void *ws, size_t ws_bytes, void *stream);
+int posfeat_pose_solve3(const double *m, double *poses);
+
 #ifdef __cplusplus
 }
 #endif

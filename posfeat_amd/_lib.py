@@ -236,6 +236,11 @@ SIGNATURES = {
                                     c_int, ctypes.c_double, ctypes.c_double, c_int,
                                     ctypes.c_uint64] + [c_void_p] * 9 + [c_size_t, c_void_p]),
     "posfeat_triangulate_dlt": (c_int, [c_void_p, c_int, c_void_p]),
+    "posfeat_ransac_pose_workspace": (c_size_t, [c_void_p, c_int, c_int]),
+    "posfeat_ransac_pose": (c_int, [c_void_p, c_ll, c_void_p, c_void_p, c_ll, c_void_p, c_void_p,
+                                    c_int, c_int, ctypes.c_double, ctypes.c_uint64, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "posfeat_pose_solve3": (c_int, [c_void_p, c_void_p]),
 }
 
 

@@ -63,6 +63,27 @@ def quat_to_rot(qvec):
                      [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
 
 
+def rot_to_quat(R):
+    """R -> COLMAP's (qw, qx, qy, qz), unit norm, qw >= 0 (quat_to_rot's
+    inverse): the component of largest magnitude from the diagonal, the others
+    from the off-diagonal sums and differences"""
+    R = np.asarray(R, np.float64).reshape(3, 3)
+    d = [R[0, 0] + R[1, 1] + R[2, 2], R[0, 0] - R[1, 1] - R[2, 2], R[1, 1] - R[0, 0] - R[2, 2],
+         R[2, 2] - R[0, 0] - R[1, 1]]
+    k = int(np.argmax(d))
+    s = 2.0 * np.sqrt(max(1.0 + d[k], 0.0))                    # 4 |q_k|
+    if k == 0:
+        q = [0.25 * s, (R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s]
+    elif k == 1:
+        q = [(R[2, 1] - R[1, 2]) / s, 0.25 * s, (R[0, 1] + R[1, 0]) / s, (R[0, 2] + R[2, 0]) / s]
+    elif k == 2:
+        q = [(R[0, 2] - R[2, 0]) / s, (R[0, 1] + R[1, 0]) / s, 0.25 * s, (R[1, 2] + R[2, 1]) / s]
+    else:
+        q = [(R[1, 0] - R[0, 1]) / s, (R[0, 2] + R[2, 0]) / s, (R[1, 2] + R[2, 1]) / s, 0.25 * s]
+    q = np.asarray(q) / np.sqrt(np.sum(np.square(q)))
+    return -q if q[0] < 0 else q
+
+
 def pose_row(qvec, t):
     """[R | t] row-major [12] of a COLMAP pose (world to camera)"""
     return np.concatenate([quat_to_rot(qvec), np.asarray(t, np.float64).reshape(3, 1)],

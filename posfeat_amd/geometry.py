@@ -35,6 +35,19 @@ score, selection, refit) are in include/posfeat_hip.h; no CPU path.
   triangulate_dlt(obs)
         the DLT of obs [n, 14] = (xu, yu, pose) rows (host only, needs no
         device): X [3], or None for a rejected system.
+  ransac_pose_queries(kp_pool, cams, points, corr, q_off, iters=1024, thr=12.0,
+                      seed=0) -> (poses [nq, 12] fp64, info [nq, 4] int32,
+                      inlier [C] uint8)
+        posfeat_ransac_pose (pose.hip): a RANSAC absolute pose (P3P, Gauss-Newton
+        refit) for every query of a list from its 2D-3D correspondences, device
+        tensors in and out, nothing read back.
+  pose_correspondences(q_rows, db_rows, point_of_row, tinfo, q_set_off)
+        the unique (query pool row, point) rows [C, 2] int32 of verified
+        query-database matches and the queries' table q_off (device, torch ops
+        only; one small read-back for the host table).
+  solve_p3p(m)
+        the P3P candidates [c, 3, 4] (c = 0..4) of three correspondences m [3, 5]
+        = (xu, yu, X, Y, Z) (host only, needs no device).
 """
 import ctypes
 
@@ -278,3 +291,92 @@ def track_edges(batch, inlier):
           (a >= 0) & (a < tab[:, 5]) & (b >= 0) & (b < tab[:, 4]))
     e = torch.stack([tab[:, 2] + a, tab[:, 3] + b], 1)
     return torch.where(ok[:, None], e, torch.full_like(e, -1)).to(torch.int32)
+
+
+def solve_p3p(m):
+    """posfeat_pose_solve3: m [3, 5] rows (xu, yu, X, Y, Z), the undistorted
+    normalised image point and the world point -> the candidate poses [c, 3, 4]
+    ([R | t], world to camera) in ascending root order; c = 0 for a rejected
+    sample."""
+    m = np.ascontiguousarray(m, dtype=np.float64)
+    if m.shape != (3, 5):
+        raise ValueError("solve_p3p takes three (xu, yu, X, Y, Z) rows")
+    out = np.zeros((4, 3, 4), dtype=np.float64)
+    c = lib().posfeat_pose_solve3(ctypes.c_void_p(m.ctypes.data), ctypes.c_void_p(out.ctypes.data))
+    if c < 0:
+        raise ValueError("posfeat_pose_solve3 failed (%d)" % c)
+    return out[:c]
+
+
+def ransac_pose_queries(kp_pool, cams, points, corr, q_off, iters=1024, thr=12.0, seed=0):
+    """posfeat_ransac_pose: kp_pool [nkp, 2] fp32 (the queries' keypoints), cams
+    [nq, 8] fp64, points [npoints, 3] fp64 (posfeat_triangulate's, as left on
+    the device), corr [C, 2] int32 = (pool row, point index) device tensors;
+    q_off [nq + 1] a host int32 table, query q owning corr[q_off[q]:q_off[q +
+    1]].  thr = 12 px is meant as COLMAP's abs_pose_max_error default (written
+    from memory, not checked against its sources).  info[q] = (status,
+    n_inliers, best_iter, refit_kept | root << 8)."""
+    _lib.require_device(kp_pool)
+    dev = kp_pool.device
+    q_off = np.ascontiguousarray(q_off, dtype=np.int32)
+    nq = q_off.shape[0] - 1
+    if kp_pool.dtype != torch.float32 or kp_pool.dim() != 2 or kp_pool.shape[1] != 2:
+        raise ValueError("kp_pool must be a [N, 2] float32 tensor")
+    if nq < 0:
+        raise ValueError("q_off needs at least one entry")
+    C = int(q_off[-1])
+    for name, t, shape, dt in (("cams", cams, (nq, 8), torch.float64),
+                               ("points", points, (points.shape[0], 3), torch.float64),
+                               ("corr", corr, (C, 2), torch.int32)):
+        if t.device != dev or t.dtype != dt or tuple(t.shape) != shape:
+            raise ValueError("%s must be a %s %s tensor on the keypoints' device" % (name, shape, dt))
+    qo = ctypes.c_void_p(q_off.ctypes.data)
+    need = lib().posfeat_ransac_pose_workspace(qo, nq, int(iters))
+    if need == 0:
+        raise ValueError("invalid query table, or iters outside 1..65536")
+    nkp, npoints = int(kp_pool.shape[0]), int(points.shape[0])
+
+    def some(t, *shape):  # the call takes no null pointer, even for an input without elements
+        return t.contiguous() if t.numel() else torch.zeros(*shape, dtype=t.dtype, device=dev)
+    kp_pool, cams, points, corr = (some(kp_pool, 1, 2), some(cams, 1, 8), some(points, 1, 3),
+                                   some(corr, 1, 2))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    poses = torch.empty(max(nq, 1), 12, dtype=torch.float64, device=dev)
+    info = torch.empty(max(nq, 1), 4, dtype=torch.int32, device=dev)
+    inlier = torch.empty(max(C, 1), dtype=torch.uint8, device=dev)
+    check(lib().posfeat_ransac_pose(
+        ptr(kp_pool), nkp, ptr(cams), ptr(points), npoints, ptr(corr), qo, nq, int(iters),
+        float(thr), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(poses), ptr(info), ptr(inlier), ptr(ws),
+        need, stream_ptr(dev)))
+    return poses[:nq], info[:nq], inlier[:C]
+
+
+def pose_correspondences(q_rows, db_rows, point_of_row, tinfo, q_set_off):
+    """The 2D-3D correspondences of the queries: match i pairs row q_rows[i] of
+    the query keypoint pool with row db_rows[i] of the database pool
+    posfeat_triangulate ran on ([M] integer device tensors; rows outside their
+    pool are ignored).  A match counts where its database row carries a point
+    (point_of_row >= 0) of status 0 with at least two inlier observations
+    (tinfo).  Returns (corr [C, 2] int32 on the device: the unique (query row,
+    point) rows in ascending order, so grouped by query; q_off [nq + 1] int32 on
+    the host for the queries' table q_set_off).  Torch ops on the device only;
+    q_off is the one read-back."""
+    dev = point_of_row.device
+    q_set_off = np.ascontiguousarray(q_set_off, dtype=np.int64)
+    nq = q_set_off.shape[0] - 1
+    N, T = int(point_of_row.shape[0]), int(tinfo.shape[0])
+    q = q_rows.to(device=dev, dtype=torch.int64).reshape(-1)
+    d = db_rows.to(device=dev, dtype=torch.int64).reshape(-1)
+    if q.numel() == 0 or N == 0 or T == 0 or nq <= 0:
+        return (torch.empty(0, 2, dtype=torch.int32, device=dev),
+                np.zeros(max(nq, 0) + 1, dtype=np.int32))
+    ok = (q >= int(q_set_off[0])) & (q < int(q_set_off[-1])) & (d >= 0) & (d < N)
+    pt = point_of_row.to(torch.int64)[d.clamp(0, N - 1)]
+    ok &= (pt >= 0) & (pt < T)
+    ti = tinfo.to(torch.int64)[pt.clamp(0, T - 1)]
+    ok &= (ti[:, 0] == 0) & (ti[:, 1] >= 2)
+    key = torch.unique(q[ok] * T + pt[ok])           # sorted
+    rows = torch.div(key, T, rounding_mode="floor")
+    corr = torch.stack([rows, key - rows * T], 1).to(torch.int32)
+    q_off = torch.searchsorted(rows, torch.from_numpy(q_set_off).to(dev))
+    return corr, q_off.cpu().numpy().astype(np.int32)
