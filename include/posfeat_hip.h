@@ -218,6 +218,7 @@ int posfeat_nms_mask(const float *score, int b, int h, int w, int radius, uint8_
  * fmap: NHWC [b][h][w] with pixel stride cstride, c channels (c <= 1024).
  * coord: [b][npts][2] normalised (x, y); n_valid: optional device int32
  *   (rows beyond *n_valid are written as zeros); out: [b][npts][c].
+ * npts == 0 is valid and launches nothing (coord and out, empty, may be null).
  * ------------------------------------------------------------------------ */
 int posfeat_sample_desc(const float *fmap, int b, int c, int h, int w, int cstride,
                         const float *coord, int npts, const int32_t *n_valid, int normalize,

@@ -10,6 +10,21 @@
 
 namespace {
 
+// Source index (grid_sampler_compute_source_index, align_corners=False) and
+// the two bilinear weights of one axis.  The index is taken in fp64, where
+// ((g + 1) * n - 1) / 2 is exact for a float32 g, so each weight carries one
+// float32 rounding.  (ATen's float32 form rounds the index itself, by up to
+// 3.2 n 2^-24 px; against an fp64 reference that moves the output by as much
+// times the difference of neighbouring taps -- 2e-6 at n = 11.)
+__device__ __forceinline__ void axis_taps(float g, int n, int& i0, float& w0, float& w1) {
+  const double ix = (((double)g + 1.0) * n - 1.0) * 0.5;
+  const double fl = floor(ix);
+  const double t = ix - fl;
+  i0 = (int)fl;
+  w0 = (float)(1.0 - t);
+  w1 = (float)t;
+}
+
 template <int CPL>  // channels per lane (C <= 64*CPL)
 __global__ void sample_desc_kernel(const float* __restrict__ fmap, int nb, int C, int h, int w,
                                    int cs, const float* __restrict__ coord, int npts,
@@ -28,15 +43,12 @@ __global__ void sample_desc_kernel(const float* __restrict__ fmap, int nb, int C
     return;
   }
   const float gx = coord[wid * 2 + 0], gy = coord[wid * 2 + 1];
-  // grid_sampler_compute_source_index, align_corners=False
-  const float ix = ((gx + 1.f) * w - 1.f) / 2.f;
-  const float iy = ((gy + 1.f) * h - 1.f) / 2.f;
-  const float fx = floorf(ix), fy = floorf(iy);
-  const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-  const float wnw = (x1 - ix) * (y1 - iy);
-  const float wne = (ix - x0) * (y1 - iy);
-  const float wsw = (x1 - ix) * (iy - y0);
-  const float wse = (ix - x0) * (iy - y0);
+  int x0, y0;
+  float wx0, wx1, wy0, wy1;
+  axis_taps(gx, w, x0, wx0, wx1);
+  axis_taps(gy, h, y0, wy0, wy1);
+  const int x1 = x0 + 1, y1 = y0 + 1;
+  const float wnw = wx0 * wy0, wne = wx1 * wy0, wsw = wx0 * wy1, wse = wx1 * wy1;
   const bool bx0 = (unsigned)x0 < (unsigned)w, bx1 = (unsigned)x1 < (unsigned)w;
   const bool by0 = (unsigned)y0 < (unsigned)h, by1 = (unsigned)y1 < (unsigned)h;
   const float* base = fmap + (long long)b * h * w * cs;
@@ -89,14 +101,12 @@ __global__ PF_NO_PK_FP32 void sample_desc128_kernel(const float* __restrict__ fm
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   if (valid) {
     const float gx = coord[kid * 2 + 0], gy = coord[kid * 2 + 1];
-    const float ix = ((gx + 1.f) * w - 1.f) / 2.f;
-    const float iy = ((gy + 1.f) * h - 1.f) / 2.f;
-    const float fx = floorf(ix), fy = floorf(iy);
-    const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-    const float wnw = (x1 - ix) * (y1 - iy);
-    const float wne = (ix - x0) * (y1 - iy);
-    const float wsw = (x1 - ix) * (iy - y0);
-    const float wse = (ix - x0) * (iy - y0);
+    int x0, y0;
+    float wx0, wx1, wy0, wy1;
+    axis_taps(gx, w, x0, wx0, wx1);
+    axis_taps(gy, h, y0, wy0, wy1);
+    const int x1 = x0 + 1, y1 = y0 + 1;
+    const float wnw = wx0 * wy0, wne = wx1 * wy0, wsw = wx0 * wy1, wse = wx1 * wy1;
     const bool bx0 = (unsigned)x0 < (unsigned)w, bx1 = (unsigned)x1 < (unsigned)w;
     const bool by0 = (unsigned)y0 < (unsigned)h, by1 = (unsigned)y1 < (unsigned)h;
     const float* base = fmap + (long long)b * h * w * cs + 4 * l32;
@@ -163,8 +173,9 @@ int pf_sample_desc(const float* fmap, int b, int c, int h, int w, int cs, const 
 extern "C" int posfeat_sample_desc(const float* fmap, int b, int c, int h, int w, int cstride,
                                    const float* coord, int npts, const int32_t* n_valid,
                                    int normalize, float* out, void* stream) {
-  if (!fmap || !coord || !out || b <= 0 || c <= 0 || h <= 0 || w <= 0 || npts < 0 || cstride < c)
-    return POSFEAT_E_INVALID;
+  if (b <= 0 || c <= 0 || h <= 0 || w <= 0 || npts < 0 || cstride < c) return POSFEAT_E_INVALID;
+  if (npts == 0) return POSFEAT_OK;  // no rows: coord and out are empty (may be null)
+  if (!fmap || !coord || !out) return POSFEAT_E_INVALID;
   return pf_sample_desc(fmap, b, c, h, w, cstride, coord, npts, n_valid, normalize, out,
                         pf_stream(stream));
 }
@@ -173,9 +184,9 @@ extern "C" int posfeat_sample_desc_each(const float* fmap, int b, int c, int h, 
                                         int cstride, const float* coord, int npts,
                                         const int32_t* n_valid, int normalize, float* out,
                                         void* stream) {
-  if (!fmap || !coord || !n_valid || !out || b <= 0 || c <= 0 || h <= 0 || w <= 0 || npts < 0 ||
-      cstride < c)
-    return POSFEAT_E_INVALID;
+  if (b <= 0 || c <= 0 || h <= 0 || w <= 0 || npts < 0 || cstride < c) return POSFEAT_E_INVALID;
+  if (npts == 0) return POSFEAT_OK;
+  if (!fmap || !coord || !n_valid || !out) return POSFEAT_E_INVALID;
   return sample_impl(fmap, b, c, h, w, cstride, coord, npts, n_valid, 1, normalize, out,
                      pf_stream(stream));
 }
