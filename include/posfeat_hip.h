@@ -1084,6 +1084,121 @@ int posfeat_ransac_pose(const float *kp, long long nkp, const double *cams, cons
                         uint8_t *inlier, void *ws, size_t ws_bytes, void *stream);
 int posfeat_pose_solve3(const double *m, double *poses);
 
+/* Points-only bundle adjustment of the tracks of posfeat_triangulate: what
+ * `colmap point_triangulator` goes on to do with fixed database poses and
+ * --Mapper.ba_refine_focal_length 0 --Mapper.ba_refine_principal_point 0
+ * --Mapper.ba_refine_extra_params 0 (evaluations/aachen/reconstruct_pipeline.py):
+ * the bundle adjustment moves only the points, observations are filtered by
+ * reprojection error and points by triangulation angle, again while the model
+ * changes.  One independent problem per track.  All in fp64.
+ * set_off is a HOST table; every other pointer is a device pointer.
+ *   kp, set_off, nsets, cams, poses   as posfeat_triangulate takes them, N =
+ *                set_off[nsets] pool rows
+ *   points_in [tmax][3], tinfo_in [tmax][4], track_off [tmax + 1], track_rows
+ *   [mmax], inlier_in [mmax], counts_in [8]   what a posfeat_triangulate call
+ *                left (its points, tinfo, track_off, track_rows, obs_inlier,
+ *                counts); T = counts_in[0] clamped to [0, tmax] is read on the
+ *                device.  None of them is written.  tmax, mmax are the
+ *                capacities of the buffers (posfeat_triangulate's Tmax, Mmax).
+ *                Track t has the m = track_off[t + 1] - track_off[t] members
+ *                track_rows[track_off[t] ..], numbered 0 .. m - 1 below; a
+ *                flag is set when its byte is not 0.  A member whose row is
+ *                outside [0, N) is never an inlier, is in no set, and nothing is
+ *                read through it.  A track whose range is not inside [0, mmax]
+ *                or has more than 1024 members (not posfeat_triangulate's) is
+ *                given status 1 and its flags are not written;
+ *   residual     of member row r in set s at the point X: posfeat_triangulate's
+ *                `camera` projection of X (distortion included) minus the
+ *                stored pixel, r = pixel(R_s X + t_s) - (x, y), and its 2 x 3
+ *                Jacobian J = (d pixel / d Xc) R_s with d pixel / d Xc the
+ *                expression of posfeat_ransac_pose's refit: with xn = xc / z, yn
+ *                = yc / z, f = 1 + k1 (xn^2 + yn^2), axx = fx (f + 2 k1 xn^2), axy
+ *                = fx 2 k1 xn yn, ayx = fy 2 k1 xn yn, ayy = fy (f + 2 k1 yn^2):
+ *                d px / d Xc = (axx, axy, -(axx xn + axy yn)) / z, d py / d Xc =
+ *                (ayx, ayy, -(ayx xn + ayy yn)) / z;
+ *   sums         over a set S of members at X: N3 = sum J^T J (six entries,
+ *                upper triangle), g = sum J^T r, cost = sum |r|^2; per member
+ *                each entry takes first the x row's product, then the y row's.
+ *                The order depends only on m: for m <= 16 the members of S in
+ *                ascending member order into one sum; for m > 16 member k of S
+ *                adds to partial sum k mod 64 in ascending k, and the 64
+ *                partial sums v[0..63] are combined by v[l] <- v[l] + v[l xor
+ *                o] for o = 32, 16, 8, 4, 2, 1 (every v[l] then holds the same
+ *                bits).  S is usable at X iff every member of S has z > 0 and a
+ *                finite |r|^2 there;
+ *   round        Levenberg-Marquardt on X over a fixed S of at least 2 members
+ *                (a smaller S leaves X alone).  Nothing happens when S is not
+ *                usable at the start.  lambda = 1e-4.  While fewer than `steps`
+ *                trial points have been evaluated and lambda <= 1e8: solve (N3
+ *                + lambda diag N3) delta = -g by Gaussian elimination with the
+ *                pivot rule of posfeat_ransac_pose's refit (partial pivoting,
+ *                the first largest entry of the column; a pivot below 1e-12
+ *                times the largest entry of its column of the damped matrix, or
+ *                not positive, or a non-finite delta: unsolvable, no trial
+ *                point is evaluated).  The step to X + delta is taken iff S is
+ *                usable there and the cost is strictly lower; then lambda <-
+ *                lambda / 10, and the round ends if max |delta_i| <= 1e-10
+ *                max(1, max |X_i|) at the new X.  A refused or unsolvable step
+ *                gives lambda <- 10 lambda.  The cost over S never rises;
+ *   rounds       a track whose input status is not 0 is carried through as
+ *                status 1.  X starts as the input point, S_1 as the input flags
+ *                (valid rows only).  Round k = 1 .. rounds: the LM round on S_k;
+ *                then every member of the track is tested at X by
+ *                posfeat_triangulate's inlier rule (thr), which gives F.  |F| <
+ *                2: status 2, stop.  F = S_k: converged, stop.  Otherwise S_k+1
+ *                = F.  The output flags are the last F; err is the mean pixel
+ *                error over F at the final X (the sum in member order over
+ *                |F|);
+ *   angle        COLMAP's filter, not the winning-pair rule: a point that is
+ *                not status 2 survives iff some pair i < j of the last F passes
+ *                posfeat_triangulate's angle test at X (both |X - C| > 0 and
+ *                the cosine < cos(min_angle_deg)); otherwise status 3.  Two rows
+ *                of one image never qualify (their centres coincide).
+ * Outputs (device, buffers of their own: no output may overlap an input):
+ *   points [tmax][3], err [tmax];
+ *   tinfo [tmax][4] = {status, n_inliers, best_h and refit_kept of tinfo_in};
+ *   obs_inlier [mmax] (parallel to track_rows), point_of_row [N] (the track id
+ *     where the row is a final inlier of a status-0 track, else -1);
+ *   rinfo [tmax][4] = {rounds used, taken steps, converged, flags changed (the
+ *     last F differs from the input flags)}, {0, 0, 0, 0} for a carried track;
+ *   counts [8] = {T, status-0 points, their inlier observations, status-2
+ *     points, status-3 points, carried status-1 points, tracks whose flags
+ *     changed, 0}.
+ * A track of status != 0 has point 0, err 0, n_inliers 0 and flags 0, as
+ * posfeat_triangulate writes a status-1 track.  Entries past T / the last
+ * track's members are not written.  track_off and track_rows are shared with
+ * the input, so the result reads like a posfeat_triangulate result.
+ * Returns, before any device work: POSFEAT_E_INVALID for a null pointer (kp for
+ * N = 0 and cams, poses for nsets = 0 may be null), a bad set table, tmax or
+ * mmax negative, tmax + 1 or mmax above INT32_MAX, a non-finite or non-positive thr,
+ * min_angle_deg outside [0, 90), rounds outside 1..8, steps outside 1..32, ws
+ * not 256-B aligned, points_in, points, err, cams or poses not 8-B aligned, an
+ * int32 buffer or kp not 4-B aligned; POSFEAT_E_WORKSPACE for ws_bytes below
+ * posfeat_refine_points_workspace (0 for invalid arguments).
+ * Three launches (and one copy of set_off) whatever T; stream-ordered, never
+ * synchronises the host; NOT graph-capturable (set_off is copied from pageable
+ * host memory).  No floating-point atomics.  Deterministic: the same inputs give
+ * the same bits, and the result for a track depends only on its own members,
+ * their cameras, its input point and flags, thr, min_angle_deg, rounds, steps.
+ * posfeat_refine_point is host only (no device, no launch) and compiles the
+ * text the kernels compile: one `round` over all n rows of obs [n][22] = (x, y,
+ * the 8 camera entries, the 12 pose entries) in the order a track of n members
+ * has, from X0 [3]; writes X [3] and the cost there (NaN when the rows are not
+ * usable at X0) and returns the number of taken steps; POSFEAT_E_INVALID for a
+ * null pointer, n < 2 or steps outside 1..32. */
+size_t posfeat_refine_points_workspace(const int32_t *set_off, int nsets, long long tmax,
+                                       long long mmax);
+int posfeat_refine_points(const float *kp, const int32_t *set_off, int nsets, const double *cams,
+                          const double *poses, const double *points_in, const int32_t *tinfo_in,
+                          const int32_t *track_off, const int32_t *track_rows,
+                          const uint8_t *inlier_in, const int32_t *counts_in, long long tmax,
+                          long long mmax, double thr, double min_angle_deg, int rounds, int steps,
+                          double *points, double *err, int32_t *tinfo, uint8_t *obs_inlier,
+                          int32_t *point_of_row, int32_t *rinfo, int32_t *counts, void *ws,
+                          size_t ws_bytes, void *stream);
+int posfeat_refine_point(const double *obs, int n, const double *X0, int steps, double *X,
+                         double *cost);
+
 #ifdef __cplusplus
 }
 #endif

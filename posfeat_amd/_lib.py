@@ -241,6 +241,11 @@ SIGNATURES = {
                                     c_int, c_int, ctypes.c_double, ctypes.c_uint64, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "posfeat_pose_solve3": (c_int, [c_void_p, c_void_p]),
+    "posfeat_refine_points_workspace": (c_size_t, [c_void_p, c_int, c_ll, c_ll]),
+    "posfeat_refine_points": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 8 +
+                              [c_ll, c_ll, ctypes.c_double, ctypes.c_double, c_int, c_int] +
+                              [c_void_p] * 8 + [c_size_t, c_void_p]),
+    "posfeat_refine_point": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
 }
 
 

@@ -282,6 +282,23 @@ PFR_HD inline void gn_zero(double (&acc)[GN_ACC]) {
   for (int i = 0; i < GN_ACC; ++i) acc[i] = 0.0;
 }
 
+// The pixel reprojection residual (pftri's forward model) of the camera point
+// (xc, yc, z) against the pixel (x, y), and its derivative by the camera point:
+// r = pixel(Xc) - (x, y), jx = d r_x / d Xc, jy = d r_y / d Xc (d pixel / d (xn,
+// yn), then d (xn, yn) / d Xc).  The pose refit below and the point refinement
+// (refine_solve.h) compile this one text.
+PFR_HD inline void pixel_jac(const double* cam, double xc, double yc, double z, double x, double y,
+                             double& rx, double& ry, double (&jx)[3], double (&jy)[3]) {
+  const double xn = xc / z, yn = yc / z, k1 = cam[4];
+  const double f = 1.0 + k1 * (xn * xn + yn * yn);
+  rx = (cam[0] * f * xn + cam[2]) - x, ry = (cam[1] * f * yn + cam[3]) - y;
+  const double axx = cam[0] * (f + 2.0 * k1 * (xn * xn)), axy = cam[0] * (2.0 * k1 * (xn * yn));
+  const double ayx = cam[1] * (2.0 * k1 * (xn * yn)), ayy = cam[1] * (f + 2.0 * k1 * (yn * yn));
+  const double iz = 1.0 / z;
+  jx[0] = axx * iz, jx[1] = axy * iz, jx[2] = -(axx * xn + axy * yn) * iz;
+  jy[0] = ayx * iz, jy[1] = ayy * iz, jy[2] = -(ayx * xn + ayy * yn) * iz;
+}
+
 // One inlier's share of the normal equations of the pixel reprojection error
 // (pftri's forward model) at the pose P: the residual r = pixel(P X) - (x, y),
 // its Jacobian J (2 x 6) against delta = (omega, tau) perturbing the camera
@@ -292,15 +309,8 @@ PFR_HD inline void gn_row(const double* cam, const double (&P)[12], double x, do
   const double xc = ((P[0] * X + P[1] * Y) + P[2] * Z) + P[3];
   const double yc = ((P[4] * X + P[5] * Y) + P[6] * Z) + P[7];
   const double z = ((P[8] * X + P[9] * Y) + P[10] * Z) + P[11];
-  const double xn = xc / z, yn = yc / z, k1 = cam[4];
-  const double f = 1.0 + k1 * (xn * xn + yn * yn);
-  const double rx = (cam[0] * f * xn + cam[2]) - x, ry = (cam[1] * f * yn + cam[3]) - y;
-  // d pixel / d (xn, yn), then d (xn, yn) / d Xc
-  const double axx = cam[0] * (f + 2.0 * k1 * (xn * xn)), axy = cam[0] * (2.0 * k1 * (xn * yn));
-  const double ayx = cam[1] * (2.0 * k1 * (xn * yn)), ayy = cam[1] * (f + 2.0 * k1 * (yn * yn));
-  const double iz = 1.0 / z;
-  const double jx[3] = {axx * iz, axy * iz, -(axx * xn + axy * yn) * iz};
-  const double jy[3] = {ayx * iz, ayy * iz, -(ayx * xn + ayy * yn) * iz};
+  double rx, ry, jx[3], jy[3];
+  pixel_jac(cam, xc, yc, z, x, y, rx, ry, jx, jy);
   // d Xc / d omega = -[Xc]x, d Xc / d tau = I
   double a[6], b[6];
   a[0] = jx[2] * yc - jx[1] * z, a[1] = jx[0] * z - jx[2] * xc, a[2] = jx[1] * xc - jx[0] * yc;
@@ -319,39 +329,35 @@ PFR_HD inline void gn_row(const double* cam, const double (&P)[12], double x, do
   acc[28] = acc[28] + ((z > 0.0 && finite_d(e2)) ? 0.0 : 1.0);
 }
 
-// N delta = -g by Gaussian elimination with partial pivoting (the first largest
-// entry of the column); false when a pivot is below GN_PIVOT_REL times the
-// largest entry of its column of N as given, or is not a positive number
-PFR_HD inline bool gn_solve(const double (&acc)[GN_ACC], double (&delta)[6]) {
-  double a[6][7], cmax[6];
-  int k = 0;
+// a[.][0..D) delta = a[.][D] (destroyed) by Gaussian elimination with partial
+// pivoting (the first largest entry of the column); false when a pivot is below
+// GN_PIVOT_REL times the largest entry of its column of the matrix as given, or
+// is not a positive number, or delta is not finite.  The pose refit (D = 6) and
+// the point refinement (D = 3, refine_solve.h) compile this one text.
+template <int D>
+PFR_HD inline bool pivot_solve(double (&a)[D][D + 1], double (&delta)[D]) {
+  double cmax[D];
 #pragma unroll
-  for (int r = 0; r < 6; ++r)
-#pragma unroll
-    for (int c = r; c < 6; ++c, ++k) a[r][c] = acc[k], a[c][r] = acc[k];
-#pragma unroll
-  for (int r = 0; r < 6; ++r) a[r][6] = -acc[21 + r];
-#pragma unroll
-  for (int c = 0; c < 6; ++c) {
+  for (int c = 0; c < D; ++c) {
     cmax[c] = fabs(a[0][c]);
 #pragma unroll
-    for (int r = 1; r < 6; ++r) cmax[c] = fmax(cmax[c], fabs(a[r][c]));
+    for (int r = 1; r < D; ++r) cmax[c] = fmax(cmax[c], fabs(a[r][c]));
   }
   bool ok = true;
 #pragma unroll
-  for (int c = 0; c < 6; ++c) {
+  for (int c = 0; c < D; ++c) {
     int piv = c;
     double best = fabs(a[c][c]);
 #pragma unroll
-    for (int r = c + 1; r < 6; ++r) {
+    for (int r = c + 1; r < D; ++r) {
       const double v = fabs(a[r][c]);
       if (v > best) best = v, piv = r;
     }
 #pragma unroll
-    for (int r = c + 1; r < 6; ++r) {
+    for (int r = c + 1; r < D; ++r) {
       const bool sw = piv == r;
 #pragma unroll
-      for (int j = c; j < 7; ++j) {
+      for (int j = c; j < D + 1; ++j) {
         const double t = a[c][j], u = a[r][j];
         a[c][j] = sw ? u : t;
         a[r][j] = sw ? t : u;
@@ -359,23 +365,37 @@ PFR_HD inline bool gn_solve(const double (&acc)[GN_ACC], double (&delta)[6]) {
     }
     ok = ok && best >= GN_PIVOT_REL * cmax[c] && best > 0.0;
 #pragma unroll
-    for (int r = c + 1; r < 6; ++r) {
+    for (int r = c + 1; r < D; ++r) {
       const double f = a[r][c] / a[c][c];
 #pragma unroll
-      for (int j = c + 1; j < 7; ++j) a[r][j] = a[r][j] - f * a[c][j];
+      for (int j = c + 1; j < D + 1; ++j) a[r][j] = a[r][j] - f * a[c][j];
     }
   }
 #pragma unroll
-  for (int c = 5; c >= 0; --c) {
-    double s = a[c][6];
+  for (int c = D - 1; c >= 0; --c) {
+    double s = a[c][D];
 #pragma unroll
-    for (int j = c + 1; j < 6; ++j) s = s - a[c][j] * delta[j];
+    for (int j = c + 1; j < D; ++j) s = s - a[c][j] * delta[j];
     delta[c] = s / a[c][c];
   }
   double tot = 0.0;
 #pragma unroll
-  for (int c = 0; c < 6; ++c) tot = tot + delta[c];
+  for (int c = 0; c < D; ++c) tot = tot + delta[c];
   return ok && finite_d(tot);
+}
+
+// N delta = -g by pivot_solve; false when a pivot is below GN_PIVOT_REL times
+// the largest entry of its column of N as given, or is not a positive number
+PFR_HD inline bool gn_solve(const double (&acc)[GN_ACC], double (&delta)[6]) {
+  double a[6][7];
+  int k = 0;
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int c = r; c < 6; ++c, ++k) a[r][c] = acc[k], a[c][r] = acc[k];
+#pragma unroll
+  for (int r = 0; r < 6; ++r) a[r][6] = -acc[21 + r];
+  return pivot_solve<6>(a, delta);
 }
 
 // Q = [exp(omega) R | exp(omega) t + tau] with exp by Rodrigues' formula: theta =

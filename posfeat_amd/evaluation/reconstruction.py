@@ -4,8 +4,8 @@ after ``geometric_verification`` (evaluations/aachen/reconstruct_pipeline.py),
 without COLMAP.
 
   triangulate_pair_list(verified_npz, feature_dir, postfix, intrinsics, nvm,
-                        thr=4.0, min_angle=1.5, iters=64, max_track=256, seed=0)
-        -> dict
+                        thr=4.0, min_angle=1.5, iters=64, max_track=256, seed=0,
+                        refine=0) -> dict
 
 ``verified_npz`` is what evaluation.verification.verify_pair_list wrote (pairs,
 match_offsets, matches); ``intrinsics`` and ``nvm`` are the two files the
@@ -15,7 +15,11 @@ MODEL w h params...``; the .nvm camera block: ``name f qw qx qy qz cx cy cz
 keypoint pool (a posed image without intrinsics raises); the verified matches
 of the pairs between them become edges (a match index outside its image's
 keypoints raises); pairs that name an image without a pose are skipped and
-counted.  geometry.triangulate_tracks runs once.  The returned dict:
+counted.  geometry.triangulate_tracks runs once.  With ``refine`` = k > 0,
+geometry.refine_tracks (points-only bundle adjustment, rounds = k, the same thr
+and min_angle) runs on its result on the device before the one read-back, and
+points, err, tinfo, obs_inlier, point_of_row and counts are the refined ones
+(counts then as posfeat_refine_points defines it).  The returned dict:
   images         [n] names; image i is set i of the pool
   set_off        [n + 1] int32
   cams, poses    [n, 8], [n, 12] fp64 as posfeat_triangulate takes them
@@ -28,6 +32,10 @@ counted.  geometry.triangulate_tracks runs once.  The returned dict:
                  mean_reprojection_error (what the reference's ETH script
                  reads from ``colmap model_analyzer``), over the points with at
                  least two inlier observations
+  with refine > 0 also:
+  rinfo          [T, 4] (rounds used, taken steps, converged, flags changed)
+  summary_unrefined   the summary of the triangulated points before refinement
+  counts_unrefined    posfeat_triangulate's counts
 write_model / read_model: COLMAP's text model (cameras.txt, images.txt,
 points3D.txt).
 """
@@ -155,7 +163,7 @@ def pair_list_edges(pairs, match_offsets, matches, index, set_off):
 
 
 def triangulate_pair_list(verified_npz, feature_dir, postfix, intrinsics, nvm, thr=4.0,
-                          min_angle=1.5, iters=64, max_track=256, seed=0):
+                          min_angle=1.5, iters=64, max_track=256, seed=0, refine=0):
     _lib.require_device()
     device = torch.device("cuda", torch.cuda.current_device())
     ver = np.load(verified_npz) if isinstance(verified_npz, (str, os.PathLike)) else verified_npz
@@ -174,10 +182,17 @@ def triangulate_pair_list(verified_npz, feature_dir, postfix, intrinsics, nvm, t
     poses = np.stack([pose_row(*nvm_poses[n]) for n in images]) if images else np.zeros((0, 12))
     edges, skipped = pair_list_edges(pairs, ver["match_offsets"], ver["matches"], index, set_off)
     kp_pool = np.concatenate(kps, 0) if kps else np.zeros((0, 2), np.float32)
-    res = geometry.triangulate_tracks(
-        torch.from_numpy(kp_pool).to(device), set_off, torch.from_numpy(cams).to(device),
-        torch.from_numpy(poses).to(device), torch.from_numpy(edges).to(device), iters=iters,
-        thr=thr, min_angle=min_angle, max_track=max_track, seed=seed).host()
+    kp_d, cams_d, poses_d = (torch.from_numpy(a).to(device) for a in (kp_pool, cams, poses))
+    res = geometry.triangulate_tracks(kp_d, set_off, cams_d, poses_d,
+                                      torch.from_numpy(edges).to(device), iters=iters, thr=thr,
+                                      min_angle=min_angle, max_track=max_track, seed=seed)
+    if int(refine) > 0:
+        res = geometry.refine_tracks(kp_d, set_off, cams_d, poses_d, res, thr=thr,
+                                     min_angle=min_angle, rounds=int(refine))
+    res = res.host()
+    unrefined = res.pop("unrefined", None)
+    if unrefined is not None:
+        res.update(summary_unrefined=summary(unrefined), counts_unrefined=unrefined["counts"])
     res.update(images=images, set_off=set_off, cams=cams, poses=poses, keypoints=kp_pool,
                models=[(intr[n][0], intr[n][1], intr[n][2], intr[n][3]) for n in images],
                qvecs=[nvm_poses[n][0] for n in images], tvecs=[nvm_poses[n][1] for n in images],

@@ -1,8 +1,10 @@
 """Robust two-view model fitting on the GPU (ransac.hip, fundamental.hip): RANSAC
 homographies or fundamental matrices for every pair of a pair list in three
-launches, on the matches matchers.match_pairs_device left on the device; and
+launches, on the matches matchers.match_pairs_device left on the device;
 tracks with one triangulated point each from the verified matches
-(triangulate.hip).  The definitions (sampler, degeneracy test, minimal solve,
+(triangulate.hip); those points refined by points-only bundle adjustment
+(refine.hip); absolute poses of queries against them (pose.hip).  The
+definitions (sampler, degeneracy test, minimal solve,
 score, selection, refit) are in include/posfeat_hip.h; no CPU path.
 
   ransac_homography_pairs(kp_pool, batch, iters=1024, thr=3.0, seed=0)
@@ -35,6 +37,16 @@ score, selection, refit) are in include/posfeat_hip.h; no CPU path.
   triangulate_dlt(obs)
         the DLT of obs [n, 14] = (xu, yu, pose) rows (host only, needs no
         device): X [3], or None for a rejected system.
+  refine_tracks(kp_pool, set_off, cams, poses, tracks, thr=4.0, min_angle=1.5,
+                rounds=3, steps=10) -> RefinedTrackResult
+        posfeat_refine_points (refine.hip): Levenberg-Marquardt on the pixel
+        reprojection error of every track's point over its inliers, the inlier
+        test again, up to ``rounds`` times, then COLMAP's angle filter; device
+        tensors in and out, nothing read back.  A TrackResult with ``rinfo``
+        that shares track_off and track_rows with ``tracks``.
+  refine_point(obs, X0, steps=10)
+        one Levenberg-Marquardt round over obs [n, 22] = (x, y, cam, pose) rows
+        from X0 (host only, needs no device): (X [3], cost, taken steps).
   ransac_pose_queries(kp_pool, cams, points, corr, q_off, iters=1024, thr=12.0,
                       seed=0) -> (poses [nq, 12] fp64, info [nq, 4] int32,
                       inlier [C] uint8)
@@ -178,6 +190,21 @@ def triangulate_dlt(obs):
     return X if r == 0 else None
 
 
+def _read_back(parts):
+    """{name: device tensor} -> {name: its bytes on the host (a uint8 numpy view)}:
+    one pinned buffer, one synchronisation"""
+    flat = [p.reshape(-1).view(torch.uint8) for p in parts.values()]
+    sizes = [int(f.numel()) for f in flat]
+    host = torch.empty(sum(sizes), dtype=torch.uint8, pin_memory=True)
+    at = 0
+    for f, n in zip(flat, sizes):
+        host[at:at + n].copy_(f, non_blocking=True)
+        at += n
+    torch.cuda.current_stream(flat[0].device).synchronize()
+    h, cuts = host.numpy(), np.cumsum([0] + sizes)
+    return {k: h[cuts[i]:cuts[i + 1]] for i, k in enumerate(parts)}
+
+
 class TrackResult:
     """What one posfeat_triangulate call left on the device, cut to the worst
     case (Tmax = min(nedges, N // 2) tracks, Mmax = min(2 nedges, N) members):
@@ -196,17 +223,7 @@ class TrackResult:
     def host(self):
         """Everything on the host as numpy arrays trimmed by ``counts``: one
         pinned copy, one synchronisation."""
-        parts = [getattr(self, k) for k in self.FIELDS]
-        flat = [p.reshape(-1).view(torch.uint8) for p in parts]
-        sizes = [int(f.numel()) for f in flat]
-        host = torch.empty(sum(sizes), dtype=torch.uint8, pin_memory=True)
-        at = 0
-        for f, n in zip(flat, sizes):
-            host[at:at + n].copy_(f, non_blocking=True)
-            at += n
-        torch.cuda.current_stream(self.counts.device).synchronize()
-        h, cuts = host.numpy(), np.cumsum([0] + sizes)
-        raw = {k: h[cuts[i]:cuts[i + 1]] for i, k in enumerate(self.FIELDS)}
+        raw = _read_back({k: getattr(self, k) for k in self.FIELDS})
         counts = raw["counts"].view(np.int32).copy()
         T, M = int(counts[0]), int(counts[1])
         return dict(
@@ -265,6 +282,123 @@ def triangulate_tracks(kp_pool, set_off, cams, poses, edges, iters=64, thr=4.0, 
         ptr(out.point_of_row), ptr(out.counts), ptr(ws), need, stream_ptr(dev)))
     out.point_of_row = out.point_of_row[:N]
     return out
+
+
+class RefinedTrackResult(TrackResult):
+    """What one posfeat_refine_points call left on the device: a TrackResult
+    (``track_off`` and ``track_rows`` are the input's own tensors) plus
+    ``rinfo`` [Tmax, 4] int32 = (rounds used, taken steps, converged, flags
+    changed).  ``counts`` is posfeat_refine_points' (T, status-0 points, inlier
+    observations, status-2, status-3, carried status-1, tracks whose flags
+    changed, 0); the member count is track_off[T]."""
+
+    FIELDS = TrackResult.FIELDS + ("rinfo",)
+    source = None        # the TrackResult that was refined (refine_tracks sets it)
+
+    def host(self):
+        """TrackResult.host() plus ``rinfo`` and, where the refined TrackResult
+        is attached, ``unrefined`` = dict(err, tinfo, counts) of it: one pinned
+        copy, one synchronisation."""
+        parts = {k: getattr(self, k) for k in self.FIELDS}
+        if self.source is not None:
+            parts.update(err0=self.source.err, tinfo0=self.source.tinfo, counts0=self.source.counts)
+        raw = _read_back(parts)
+        counts = raw["counts"].view(np.int32).copy()
+        T = int(counts[0])
+        track_off = raw["track_off"].view(np.int32)[:T + 1].copy()
+        M = int(track_off[T]) if T > 0 else 0
+        out = dict(
+            points=raw["points"].view(np.float64).reshape(-1, 3)[:T].copy(),
+            err=raw["err"].view(np.float64)[:T].copy(),
+            tinfo=raw["tinfo"].view(np.int32).reshape(-1, 4)[:T].copy(),
+            track_off=track_off,
+            track_rows=raw["track_rows"].view(np.int32)[:M].copy(),
+            obs_inlier=raw["obs_inlier"][:M].copy(),
+            point_of_row=raw["point_of_row"].view(np.int32)[:self.point_of_row.shape[0]].copy(),
+            counts=counts,
+            rinfo=raw["rinfo"].view(np.int32).reshape(-1, 4)[:T].copy())
+        if self.source is not None:
+            out["unrefined"] = dict(err=raw["err0"].view(np.float64)[:T].copy(),
+                                    tinfo=raw["tinfo0"].view(np.int32).reshape(-1, 4)[:T].copy(),
+                                    counts=raw["counts0"].view(np.int32).copy())
+        return out
+
+
+def refine_tracks(kp_pool, set_off, cams, poses, tracks, thr=4.0, min_angle=1.5, rounds=3, steps=10):
+    """posfeat_refine_points on what ``tracks`` (a TrackResult of
+    triangulate_tracks on the same kp_pool, set_off, cams and poses) holds on the
+    device.  thr and min_angle as in triangulate_tracks; ``rounds`` in 1..8
+    alternations of refinement and inlier test, ``steps`` in 1..32 trial points
+    per round."""
+    _lib.require_device(kp_pool)
+    dev = kp_pool.device
+    set_off = np.ascontiguousarray(set_off, dtype=np.int32)
+    nsets = set_off.shape[0] - 1
+    if kp_pool.dtype != torch.float32 or kp_pool.dim() != 2 or kp_pool.shape[1] != 2:
+        raise ValueError("kp_pool must be a [N, 2] float32 tensor")
+    if nsets < 0 or kp_pool.shape[0] != int(set_off[-1]):
+        raise ValueError("kp_pool must have set_off[-1] rows")
+    poses = poses.reshape(-1, 12)
+    for name, t, shape, dt in (("cams", cams, (nsets, 8), torch.float64),
+                               ("poses", poses, (nsets, 12), torch.float64)):
+        if t.device != dev or t.dtype != dt or tuple(t.shape) != shape:
+            raise ValueError("%s must be a %s %s tensor on the keypoints' device" % (name, shape, dt))
+    N = int(set_off[-1])
+    tmax, mmax = int(tracks.track_off.shape[0]) - 1, int(tracks.track_rows.shape[0])
+    for name, dt, shape in (("points", torch.float64, (tracks.points.shape[0], 3)),
+                            ("tinfo", torch.int32, (tracks.points.shape[0], 4)),
+                            ("track_off", torch.int32, (tmax + 1,)),
+                            ("track_rows", torch.int32, (mmax,)),
+                            ("obs_inlier", torch.uint8, (mmax,)), ("counts", torch.int32, (8,))):
+        t = getattr(tracks, name)
+        if t.device != dev or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError("tracks.%s must be a contiguous %s %s tensor on the keypoints' device"
+                             % (name, shape, dt))
+    if tmax < 0 or tracks.points.shape[0] < max(tmax, 1) or tuple(tracks.point_of_row.shape) != (N,):
+        raise ValueError("tracks does not belong to this keypoint pool")
+    kp_pool, cams, poses = (t.contiguous() for t in (kp_pool, cams, poses))
+    so = ctypes.c_void_p(set_off.ctypes.data)
+    need = lib().posfeat_refine_points_workspace(so, nsets, tmax, mmax)
+    if need == 0:
+        raise ValueError("invalid set table")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    out = RefinedTrackResult(
+        points=torch.empty(max(tmax, 1), 3, dtype=torch.float64, device=dev),
+        err=torch.empty(max(tmax, 1), dtype=torch.float64, device=dev),
+        tinfo=torch.empty(max(tmax, 1), 4, dtype=torch.int32, device=dev),
+        track_off=tracks.track_off, track_rows=tracks.track_rows,
+        obs_inlier=torch.empty(max(mmax, 1), dtype=torch.uint8, device=dev),
+        point_of_row=torch.empty(max(N, 1), dtype=torch.int32, device=dev),
+        counts=torch.empty(8, dtype=torch.int32, device=dev),
+        rinfo=torch.empty(max(tmax, 1), 4, dtype=torch.int32, device=dev))
+    check(lib().posfeat_refine_points(
+        ptr(kp_pool), so, nsets, ptr(cams), ptr(poses), ptr(tracks.points), ptr(tracks.tinfo),
+        ptr(tracks.track_off), ptr(tracks.track_rows), ptr(tracks.obs_inlier), ptr(tracks.counts),
+        tmax, mmax, float(thr), float(min_angle), int(rounds), int(steps), ptr(out.points),
+        ptr(out.err), ptr(out.tinfo), ptr(out.obs_inlier), ptr(out.point_of_row), ptr(out.rinfo),
+        ptr(out.counts), ptr(ws), need, stream_ptr(dev)))
+    out.point_of_row = out.point_of_row[:N]
+    out.source = tracks
+    return out
+
+
+def refine_point(obs, X0, steps=10):
+    """posfeat_refine_point: obs [n >= 2, 22] rows (x, y, the 8 camera entries,
+    the 12 entries of [R | t] row-major), X0 [3] -> (X [3], the cost sum |r|^2 at
+    X, the number of taken steps) after one Levenberg-Marquardt round over all
+    rows; the cost is NaN (and X = X0) when a row has no positive depth or no
+    finite residual at X0."""
+    obs = np.ascontiguousarray(obs, dtype=np.float64)
+    X0 = np.ascontiguousarray(X0, dtype=np.float64).reshape(-1)
+    if obs.ndim != 2 or obs.shape[1] != 22 or obs.shape[0] < 2 or X0.shape[0] != 3:
+        raise ValueError("refine_point takes [n >= 2, 22] rows (x, y, cam, pose) and a point [3]")
+    X, cost = np.zeros(3, dtype=np.float64), np.zeros(1, dtype=np.float64)
+    r = lib().posfeat_refine_point(ctypes.c_void_p(obs.ctypes.data), obs.shape[0],
+                                   ctypes.c_void_p(X0.ctypes.data), int(steps),
+                                   ctypes.c_void_p(X.ctypes.data), ctypes.c_void_p(cost.ctypes.data))
+    if r < 0:
+        raise ValueError("posfeat_refine_point failed (%d): steps outside 1..32?" % r)
+    return X, float(cost[0]), int(r)
 
 
 def track_edges(batch, inlier):

@@ -3,11 +3,14 @@ reference's ``colmap point_triangulator`` step of
 evaluations/aachen/reconstruct_pipeline.py, on the GPU and without COLMAP):
 ``python triangulate_pairs.py --verified verified.npz --features DIR --postfix NAME
 --intrinsics database_intrinsics.txt --nvm MODEL.nvm --out MODEL_DIR [--thr T]
-[--min_angle DEG] [--iters N] [--max_track M] [--seed S]``.
+[--min_angle DEG] [--iters N] [--max_track M] [--seed S] [--refine K]``.
 verified.npz is what verify_pairs.py wrote; DIR holds ``<image name>.<postfix>``
 as extract.py wrote them.  Writes COLMAP's text model (cameras.txt, images.txt,
 points3D.txt) to MODEL_DIR and prints the summary
-posfeat_amd.evaluation.reconstruction.triangulate_pair_list describes."""
+posfeat_amd.evaluation.reconstruction.triangulate_pair_list describes.  With
+--refine K (K > 0) the points are refined by K rounds of points-only bundle
+adjustment on the GPU first (COLMAP's step after the triangulation); without
+it the output is the triangulated points as before."""
 import argparse
 
 from posfeat_amd.evaluation import reconstruction
@@ -25,15 +28,23 @@ if __name__ == "__main__":
     parser.add_argument("--iters", type=int, default=64)
     parser.add_argument("--max_track", type=int, default=256)
     parser.add_argument("--seed", type=int, default=0)
+    parser.add_argument("--refine", type=int, default=0)
     args = parser.parse_args()
     res = reconstruction.triangulate_pair_list(
         args.verified, args.features, args.postfix, args.intrinsics, args.nvm, thr=args.thr,
-        min_angle=args.min_angle, iters=args.iters, max_track=args.max_track, seed=args.seed)
+        min_angle=args.min_angle, iters=args.iters, max_track=args.max_track, seed=args.seed,
+        refine=args.refine)
     reconstruction.write_model(res, args.out)
-    s, c = res["summary"], res["counts"]
+    s, c = res["summary"], res.get("counts_unrefined", res["counts"])
     print("# Images: {:d}, skipped pairs: {:d}, tracks: {:d} (dropped {:d}, ignored edges {:d})".format(
         len(res["images"]), res["skipped_pairs"], int(c[0]), int(c[4]), int(c[5])))
     print("# Points: {:d}\n# Observations: {:d}\n# Mean track length: {:.6f}\n"
           "# Mean reprojection error: {:.6f}px".format(
               s["points"], s["observations"], s["mean_track_length"],
               s["mean_reprojection_error"]))
+    if args.refine > 0:
+        r, u = res["counts"], res["summary_unrefined"]
+        print("# Refined: {:d} rounds at the most, {:d} tracks changed their inliers, {:d} fell below "
+              "two inliers, {:d} failed the angle filter\n# Before refinement: {:d} points, "
+              "{:.6f}px".format(args.refine, int(r[6]), int(r[3]), int(r[4]), u["points"],
+                               u["mean_reprojection_error"]))
