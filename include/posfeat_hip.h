@@ -614,6 +614,13 @@ int posfeat_adam(float *p, const float *g, float *m, float *v, long long n, floa
 size_t posfeat_disk_flash_lse_workspace(int b, int n);
 int posfeat_disk_flash_lse(const float *fa, const float *fb, int b, int n, float T, float *lse,
                            void *ws, size_t ws_bytes, void *stream);
+/* The launch plan of the flash passes for b pairs of n points (host only, no
+ * device needed): the number of A-row splits and the rows each owns, as
+ * posfeat_disk_loss[_grad] (n = (H / 8)(W / 8)) and posfeat_disk_flash_lse
+ * launch them.  Split s covers rows [s * rows_per_split, (s + 1) *
+ * rows_per_split) of all n points in the LSE passes and of the accepted
+ * points in the SUM passes. */
+int posfeat_disk_flash_plan(int b, int n, int *nsplit, int *rows_per_split);
 
 /* ---- evaluation matchers ---------------------------------
  * Replaces mnn_matcher (losses/preprocess_utils.py:795-803 =

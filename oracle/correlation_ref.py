@@ -1,5 +1,7 @@
-"""torch-CPU fp32 restatement of the training-side descriptor correlation
-(TEST ORACLE).  Random draws are explicit inputs so the same values can be
+"""torch-CPU restatement of the training-side descriptor correlation
+(TEST ORACLE), fp32 as the reference runs it; the DiskLoss part follows the
+dtype of the maps passed in (float64 maps give the fp64 reference of
+tests/disk_fixture.py).  Random draws are explicit inputs so the same values can be
 fed to the HIP kernels:
 
 * ``grid_points``            generate_kpts_regular_grid_random(_single),
@@ -27,7 +29,7 @@ def gen_grid(h_min, h_max, w_min, w_max, len_h, len_w):
 
 
 def normalize_coords(coord, h, w):
-    c = torch.tensor([(w - 1) / 2.0, (h - 1) / 2.0], dtype=torch.float32)
+    c = torch.tensor([(w - 1) / 2.0, (h - 1) / 2.0], dtype=coord.dtype)
     return (coord - c) / c
 
 
@@ -41,7 +43,7 @@ def homogenize(coord):
 
 
 def sample_feat(x, coord_n, norm):
-    f = F.grid_sample(x, coord_n.unsqueeze(2), padding_mode="zeros", align_corners=False).squeeze(-1)
+    f = F.grid_sample(x, coord_n.to(x.dtype).unsqueeze(2), padding_mode="zeros", align_corners=False).squeeze(-1)
     if norm:
         f = F.normalize(f, p=2, dim=1)
     return f.transpose(1, 2)
@@ -202,7 +204,7 @@ def disk_point_logp(kp_map, g, proposals, accept):
     ry, rx = proposals // g, proposals % g
     iy = torch.arange(h // g).view(1, 1, -1, 1) * g + ry
     ix = torch.arange(w // g).view(1, 1, 1, -1) * g + rx
-    kps = torch.stack([ix.float(), iy.float()], -1).reshape(b, -1, 2)
+    kps = torch.stack([ix, iy], -1).reshape(b, -1, 2).to(kp_map.dtype)
     return kps, plogp + alogp
 
 

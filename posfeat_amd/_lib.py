@@ -208,6 +208,8 @@ SIGNATURES = {
     "posfeat_disk_flash_lse_workspace": (c_size_t, [c_int, c_int]),
     "posfeat_disk_flash_lse": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_void_p,
                                        c_void_p, c_size_t, c_void_p]),
+    "posfeat_disk_flash_plan": (c_int, [c_int, c_int, ctypes.POINTER(c_int),
+                                        ctypes.POINTER(c_int)]),
     "posfeat_match": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, ctypes.c_float,
                               c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "posfeat_match_pairs_workspace": (c_size_t, [c_void_p, c_int, c_void_p, c_int]),
@@ -353,6 +355,15 @@ def conv_plan_query(n, h, w, cin, cout, k, stride, pad, wplanes=False, tile=-1, 
     out = {f: getattr(info, f) for f, _ in ConvPlanInfo._fields_}
     out["kernel"] = out["kernel"].decode()
     return out
+
+
+def disk_flash_plan(b, n):
+    """(nsplit, rows_per_split) of DiskLoss's flash passes for b pairs of n
+    points (host only, no device needed), or None for b or n <= 0."""
+    ns, rps = c_int(), c_int()
+    if lib().posfeat_disk_flash_plan(b, n, ctypes.byref(ns), ctypes.byref(rps)) != 0:
+        return None
+    return ns.value, rps.value
 
 
 def model_specs():

@@ -1006,6 +1006,19 @@ int flash_nsplit(int n, int nb) {
   return best;
 }
 
+// The flash passes' launch plan: the split count and the A rows each split
+// owns (whole FSTEP steps; the last split may be short or, in the SUM passes
+// over the accepted points only, empty).  The one place both are computed:
+// the loss, the stand-alone LSE pass, their workspace sizes and the host query
+// posfeat_disk_flash_plan all read it.
+struct FlashPlan {
+  int nsplit, rows_per_split;
+};
+FlashPlan flash_plan(int b, int n) {
+  const int ns = flash_nsplit(n, b);
+  return {ns, ((n + ns - 1) / ns + FSTEP - 1) / FSTEP * FSTEP};
+}
+
 // read per call (a few getenv per loss) so tests can A/B both paths in-process
 // the flash passes' product arithmetic follows the conv precision mode
 // (posfeat_set_conv_precision: >= 1 bf16x6, the default; 0 fp32 MFMA)
@@ -1049,7 +1062,7 @@ static size_t disk_common_bytes(size_t b, size_t n) {
 }
 
 static size_t disk_flash_bytes(size_t b, size_t n) {  // flash path scratch after the common part
-  const size_t ns = (size_t)flash_nsplit((int)n, (int)b);
+  const size_t ns = (size_t)flash_plan((int)b, (int)n).nsplit;
   return pf_align(b * ns * n * 8, 256) +            // LSE partials (max, sum)
          pf_align(b * ns * n * 4, 256) +            // reward p partials
          pf_align(b * ns * n * 8, 256) +            // reinforce partials (fp64)
@@ -1132,7 +1145,8 @@ static int disk_loss_impl(const float* kp1, const float* kp2, const float* xf1, 
                      ln2);
   PF_CHECK_LAUNCH();
   if (use_flash()) {
-    const int ns = flash_nsplit(n, b);
+    const FlashPlan plan = flash_plan(b, n);
+    const int ns = plan.nsplit;
     float2* lsep = static_cast<float2*>(take((size_t)b * ns * n * 8));
     float* gp = static_cast<float*>(take((size_t)b * ns * n * 4));
     double* rp = static_cast<double*>(take((size_t)b * ns * n * 8));
@@ -1151,11 +1165,10 @@ static int disk_loss_impl(const float* kp1, const float* kp2, const float* xf1, 
       flash_split(f1, b, n, pl1, st);
       flash_split(f2, b, n, pl2, st);
     }
-    const int rps = ((n + ns - 1) / ns + FSTEP - 1) / FSTEP * FSTEP;
     const dim3 fgrid((n + FCOLS - 1) / FCOLS, ns, b);
     FlashArgs fa{};
     fa.n = n;
-    fa.rows_per_split = rps;
+    fa.rows_per_split = plan.rows_per_split;
     fa.T = temperature;
     fa.thr = reward_thr;
     fa.good = good_reward;
@@ -1272,12 +1285,22 @@ static int disk_loss_impl(const float* kp1, const float* kp2, const float* xf1, 
   return POSFEAT_OK;
 }
 
+// Pure host query of the flash passes' plan for b pairs of n points (no device
+// needed): what posfeat_disk_loss[_grad] and posfeat_disk_flash_lse launch.
+extern "C" int posfeat_disk_flash_plan(int b, int n, int* nsplit, int* rows_per_split) {
+  if (b <= 0 || n <= 0 || !nsplit || !rows_per_split) return POSFEAT_E_INVALID;
+  const FlashPlan plan = flash_plan(b, n);
+  *nsplit = plan.nsplit;
+  *rows_per_split = plan.rows_per_split;
+  return POSFEAT_OK;
+}
+
 // The flash LSE pass on its own (the softmax normaliser of DiskLoss,
 // kploss.py:160-166): lse[b][j] = logsumexp_i(T <fa_i, fb_j> - T) over the n
 // rows of fa, for each of the n rows of fb; fa, fb [b][n][128] L2-normalised.
 extern "C" size_t posfeat_disk_flash_lse_workspace(int b, int n) {
   if (b <= 0 || n <= 0) return 0;
-  return pf_align((size_t)b * flash_nsplit(n, b) * n * 8, 256) +
+  return pf_align((size_t)b * flash_plan(b, n).nsplit * n * 8, 256) +
          2 * pf_align((size_t)b * n * FD * 6, 256);  // bf16x6 planes of fa / fb
 }
 
@@ -1286,7 +1309,8 @@ extern "C" int posfeat_disk_flash_lse(const float* fa, const float* fb, int b, i
   if (!fa || !fb || !lse || !ws || b <= 0 || n <= 0) return POSFEAT_E_INVALID;
   if (ws_bytes < posfeat_disk_flash_lse_workspace(b, n)) return POSFEAT_E_WORKSPACE;
   hipStream_t st = pf_stream(stream);
-  const int ns = flash_nsplit(n, b);
+  const FlashPlan plan = flash_plan(b, n);
+  const int ns = plan.nsplit;
   FlashArgs fa_{};
   char* pw = static_cast<char*>(ws) + pf_align((size_t)b * ns * n * 8, 256);
   unsigned short* pla = reinterpret_cast<unsigned short*>(pw);
@@ -1298,7 +1322,7 @@ extern "C" int posfeat_disk_flash_lse(const float* fa, const float* fb, int b, i
   fa_.A = FlashSide{fa, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, pla};
   fa_.B = FlashSide{fb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, plb};
   fa_.n = n;
-  fa_.rows_per_split = ((n + ns - 1) / ns + FSTEP - 1) / FSTEP * FSTEP;
+  fa_.rows_per_split = plan.rows_per_split;
   fa_.T = T;
   fa_.lse_part = static_cast<float2*>(ws);
   launch_flash<false>(dim3((n + FCOLS - 1) / FCOLS, ns, b), st, fa_, 0);
