@@ -1206,6 +1206,161 @@ int posfeat_refine_points(const float *kp, const int32_t *set_off, int nsets, co
 int posfeat_refine_point(const double *obs, int n, const double *X0, int steps, double *X,
                          double *cost);
 
+/* Five-point RANSAC essential matrices and relative poses for every pair of a
+ * list whose cameras are calibrated: the two-view problem between
+ * posfeat_ransac_fundamental (no calibration) and posfeat_triangulate (known
+ * poses), and what a relative-pose AUC is computed from.  kp, set_off, pairs,
+ * matches, counts, iters, seed, ws and stream mean what they mean for
+ * posfeat_ransac_fundamental; cams [nsets][8] fp64 is posfeat_triangulate's
+ * camera row (fx, fy, cx, cy, k1, 0, 0, 0), one per set, on the device.  Per
+ * pair p = (s1, s2) with n = counts[p] matches, all in fp64, contraction off:
+ *   coordinates  every match whose indices are inside their sets is
+ *                undistorted on both sides as posfeat_triangulate undistorts
+ *                (8 Newton steps on the SIMPLE_RADIAL model) into normalised
+ *                camera coordinates x1 = (x, y, 1), x2 = (u, v, 1).  A match
+ *                outside its sets, or with a non-finite undistorted point, is
+ *                a NaN row: it rejects any sample that draws it and is never
+ *                an inlier.  No further normalisation: calibrated coordinates
+ *                are of order one;
+ *   threshold    COLMAP's rule for calibrated pairs: thr_n = (thr / f1 + thr /
+ *                f2) / 2 with fi = (fx_i + fy_i) / 2, thr in pixels;
+ *   sampler      iteration `it` draws the five distinct match indices
+ *                posfeat_ransac_sample_k(seed, p, it, n, 5, out) gives;
+ *   system       row i of the 5x9 system A e = 0 is (u x, u y, u, v x, v y, v,
+ *                x, y, 1) of sample match i, e = E row-major (x2^T E x1 = 0);
+ *   null space   posfeat_ransac_fundamental's elimination with full pivoting
+ *                (the same pivot, tie and 1e-12 rejection rule) over s = 0..4;
+ *                the four columns left at positions 5..8 are free: e_j (j =
+ *                0..3) has 1 at position 5 + j and 0 at the other three, the
+ *                rest by back substitution, then the column swaps undone.  The
+ *                basis is E_i = sum_j M[i][j] e_j with the fixed orthogonal M =
+ *                I - w w^T / 27, w = (-2, -4, -5, 3), whose last row is (2, 4,
+ *                5, 6) / 9 (the sum over j in ascending order, each M[i][j] the
+ *                quotient of an integer by 27);
+ *   constraints  E = x E_0 + y E_1 + z E_2 + E_3.  Linear polynomials are held
+ *                over (x, y, z, 1), quadratic ones over (x^2, xy, xz, x, y^2,
+ *                yz, y, z^2, z, 1), cubic ones over the twenty monomials (x^3,
+ *                y^3, x^2 y, x y^2, x^2 z, x^2, y^2 z, y^2, xyz, xy, x z^2, xz,
+ *                x, y z^2, yz, y, z^3, z^2, z, 1).  A product of two linear
+ *                polynomials sums a[i] b[j] over i then j; a cubic accumulates
+ *                s (q[k] l[j]) over k then j.  Row 0 of the 10x20 matrix is det
+ *                E expanded along its first row (minors (E11 E22 - E12 E21),
+ *                (E10 E22 - E12 E20), (E10 E21 - E11 E20), signs + - +); row 1 +
+ *                3 i + j is the entry (i, j) of 2 E E^T E - tr(E E^T) E, with (E
+ *                E^T)_ik the sum of three products in column order, the three
+ *                terms 2 (E E^T)_ik E_kj in k order and then -tr E_ij;
+ *   elimination  Nister's route: Gauss-Jordan on the first ten columns with
+ *                partial pivoting (the first largest |entry| of column s in
+ *                rows >= s; row s divided by it; column s cleared in every
+ *                other row).  The sample is rejected when a pivot is below
+ *                1e-12 times the largest |entry| of the matrix as formed or is
+ *                not a positive number.  With e..j rows 4..9 of the result, the
+ *                rows e - z f, g - z h, i - z j form the 3x3 matrix B(z) whose
+ *                columns multiply (x, y, 1), of degrees (3, 3, 4) in z; its
+ *                determinant, expanded along the first row with polynomial
+ *                products summed over i then j, is the degree-10 polynomial c;
+ *   roots        no root when a coefficient is not finite or |c10| <= 1e-12
+ *                max |ck|.  On the monic a = c / c10, Aberth-Ehrlich in complex
+ *                arithmetic (products and quotients by the textbook formulas):
+ *                the ten estimates start at r0 (cos t_k, sin t_k), t_k = 2 pi k
+ *                / 10 + 0.7, r0 = max_k |a[10-k]|^(1/k) (1 when that is 0); a
+ *                sweep visits i = 0..9 in order, each with the estimates as
+ *                they stand: p and p' at z_i by Horner, nothing for p = 0, else
+ *                w = p / p', s = sum_{j != i} 1 / (z_i - z_j), z_i -= w / (1 - w
+ *                s) when that is finite.  40 sweeps, always all of them: a
+ *                fixed operation count, the same text on host and device, no
+ *                library eigen-solver.  z_i is real iff |Im z_i| <= 1e-8 max(1,
+ *                |z_i|); its real part then takes two Newton steps on the real
+ *                monic polynomial (a step with a zero derivative or a
+ *                non-finite result is skipped).  Per real root in ascending z:
+ *                B(z) by Horner, the cross products of its rows (0, 1), (0, 2),
+ *                (1, 2); the first with the largest |third component| gives x =
+ *                c0 / c2, y = c1 / c2.  (x, y, z) then takes three Gauss-Newton
+ *                steps on the ten cubics themselves (the 10x20 matrix as it
+ *                was before the elimination): mon_k = (x^a y^b) z^c, r = A mon,
+ *                J = A dmon/d(x, y, z), N = J^T J, g = J^T r, delta = adj(N) g /
+ *                det N by cofactors, (x, y, z) -= delta; a step with a zero
+ *                determinant or a non-finite delta is skipped.  This removes
+ *                the rounding the elimination and the polynomial's coefficients
+ *                leave on an ill-conditioned sample.  E = ((x E_0 + y E_1) + z
+ *                E_2) + E_3,
+ *                scaled to Frobenius norm 1 with the first largest entry
+ *                positive.  A root whose E is not finite or zero is dropped.
+ *                The survivors in that order are candidates 0..9; a sample
+ *                without one counts as rejected;
+ *   score        a match is an inlier iff its squared Sampson distance under E
+ *                in normalised coordinates is finite and <= thr_n^2,
+ *                evaluated as posfeat_ransac_fundamental evaluates it;
+ *   selection    most inliers, ties to the lowest iteration, then to the lowest
+ *                candidate index;
+ *   refit        the linear fit over the winner's inliers exactly as
+ *                posfeat_ransac_fundamental's refit (normal matrix of the rows
+ *                of `system` in a fixed order, 9x9 Jacobi, rank 2), in the
+ *                normalised camera coordinates themselves; then `project`, then
+ *                the output scaling.  Kept iff the winner has at least 8
+ *                inliers, the result is finite and not zero, and its inlier
+ *                count is >= the winner's;
+ *   project      the same Jacobi on E^T E (3x3); v1, v2 the eigenvectors of
+ *                the largest and second largest diagonal entry (the first of
+ *                equal ones first), v3 = v1 x v2; u_i = E v_i / |E v_i| for i =
+ *                1, 2, u3 = u1 x u2; E <- u1 v1^T + u2 v2^T.  The two largest
+ *                singular values of an essential matrix are equal, so which
+ *                eigenvector comes first is decided by rounding: when the
+ *                first largest-magnitude entry of u3 is negative, (u1, u2) and
+ *                (v1, v2) are swapped and u3, v3 negated.  U = (u1 u2 u3) and
+ *                V = (v1 v2 v3) have determinant +1;
+ *   pose         U and V of `project` run on the output E.  The four
+ *                decompositions in the order (U W V^T, +u3), (U W V^T, -u3), (U
+ *                W^T V^T, +u3), (U W^T V^T, -u3), W = [0 -1 0; 1 0 0; 0 0 1].
+ *                For each, every inlier match is triangulated between [I | 0]
+ *                and [R | t]: with a = R x1, the two rows d1 (a0 - u a2) = u t2
+ *                - t0 and d1 (a1 - v a2) = v t2 - t1 give the least-squares
+ *                depth d1 = (p . q) / (p . p) in view 1, and d2 = r3 . (d1 x1) +
+ *                t2 in view 2 (posfeat_triangulate's depth).  A match is in
+ *                front when both are finite and positive; the decomposition
+ *                with the most such inliers wins, ties to the lowest index.
+ * Outputs (device): E [npairs][9] row-major, scaled as above; pose [npairs][12]
+ * the row-major [R | t] with x2 ~ R x1 + t and |t| = 1; info [npairs][4] =
+ * {status, n_inliers, best_iter, refit_kept | root << 8}; cheir [npairs][2] =
+ * {decomposition index, n_front}; inlier as posfeat_ransac_fundamental lays it
+ * out.  status 1 (fewer than 5 matches, or every sample rejected): E and pose
+ * 0, info {1, 0, -1, 0}, cheir {-1, 0}, mask 0.
+ * Returns, before any device work, what posfeat_ransac_fundamental returns for
+ * the same mistakes (a null cams is one); E, pose and cams must be 8-B aligned.
+ * posfeat_ransac_essential_workspace is 0 for an invalid table or iteration
+ * count; the workspace holds 10 candidate records of 80 B per iteration and
+ * pair, about 0.8 MB per pair at 1024 iterations.
+ * Four launches (and one copy of the pair table) whatever npairs;
+ * stream-ordered, never synchronises the host; NOT graph-capturable.  No
+ * atomics.  Deterministic: the same inputs give the same bits, and the result
+ * for a pair index does not depend on the other pairs of the list.
+ * Limitations: the gauge (coefficient 1 on E_3) cannot reach a solution whose
+ * free entries f satisfy 2 f5 + 4 f6 + 5 f7 + 6 f8 = 0; M is there so that no
+ * zero pattern and no symmetric or skew-symmetric pair of entries (every pure
+ * translation) produces this, which leaves a measure-zero set.  Under pure
+ * rotation every t fits: the inlier count is still well defined, the pose's t
+ * is not, and n_front is not meaningful.
+ * posfeat_essential_solve5 and posfeat_essential_decompose are host only (no
+ * device, no launch) and compile the text the kernels compile, with the host's
+ * pow.  posfeat_essential_solve5 runs `system` to `roots` on m [5][4] = (x, y,
+ * u, v) rows in normalised camera coordinates, writes the candidates to E [<=
+ * 10][9] and returns their number: 0 for a rejected sample or a non-finite
+ * row, POSFEAT_E_INVALID for a null pointer.  posfeat_essential_decompose runs
+ * `pose` on E [9] over all n rows of m [n][4], writes pose [12] and front [2] =
+ * {decomposition index, n_front}; POSFEAT_E_INVALID for a null pointer (m may
+ * be null for n = 0), n < 0, or an E whose decompositions are not finite. */
+int posfeat_essential_solve5(const double *m, double *E);
+int posfeat_essential_decompose(const double *E, const double *m, int n, double *pose,
+                                int32_t *front);
+size_t posfeat_ransac_essential_workspace(const int32_t *set_off, int nsets,
+                                          const int32_t *pairs, int npairs, int iters);
+int posfeat_ransac_essential(const float *kp, const double *cams, const int32_t *set_off,
+                             int nsets, const int32_t *pairs, int npairs,
+                             const int32_t *matches, const int32_t *counts, int iters,
+                             double thr, uint64_t seed, double *E, double *pose, int32_t *info,
+                             int32_t *cheir, uint8_t *inlier, void *ws, size_t ws_bytes,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -229,6 +229,13 @@ SIGNATURES = {
                                            c_void_p, c_int, ctypes.c_double, ctypes.c_uint64,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                            c_void_p]),
+    "posfeat_essential_solve5": (c_int, [c_void_p, c_void_p]),
+    "posfeat_essential_decompose": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "posfeat_ransac_essential_workspace": (c_size_t, [c_void_p, c_int, c_void_p, c_int, c_int]),
+    "posfeat_ransac_essential": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                         c_void_p, c_void_p, c_int, ctypes.c_double,
+                                         ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_size_t, c_void_p]),
     "posfeat_ransac_homography": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                           c_void_p, c_int, ctypes.c_double, ctypes.c_uint64,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,

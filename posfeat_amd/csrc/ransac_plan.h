@@ -162,4 +162,53 @@ inline int build_plan_fundamental(const int32_t* set_off, int nsets, const int32
   return build_plan(set_off, nsets, pairs, npairs, iters, pl);
 }
 
+// The slot key of posfeat_ransac_essential (essential.hip): a sample yields up
+// to ten models, so four bits hold the root index.  The order is
+// slot_key_root's: more inliers, then the lower iteration, then the lower root.
+PFR_HD inline unsigned long long slot_key_root4(int cnt, int it, int root) {
+  return ((unsigned long long)(unsigned)(cnt + 1) << 32) |
+         (0xffffffffu - (((unsigned)it << 4) | (unsigned)root));
+}
+PFR_HD inline int slot_key_iter4(unsigned long long key) {
+  return (int)((0xffffffffu - (unsigned)key) >> 4);
+}
+PFR_HD inline int slot_key_rootidx4(unsigned long long key) {
+  return (int)((0xffffffffu - (unsigned)key) & 15u);
+}
+
+// The plan of posfeat_ransac_essential: the same Pair table (pad[0], pad[1]
+// carry the two set indices, for the cameras) and hypothesis blocks; its own
+// workspace, each region 256-B aligned:
+//   [0, pts_off)                   Pair table (uploaded per call)
+//   [pts_off, +32 * M)             per match row x y u v fp64, undistorted
+//   [cnt_off, +4 * npairs * nblk)  candidate records of each hypothesis block
+//   [rec_off, +EREC_BYTES * EBLOCK_RECS * npairs * nblk)  the records: per
+//                                  block EBLOCK_RECS of 10 doubles (key, E)
+//   [slot_off, +8 * npairs * nblk * ESUB)  per (pair, block, 256 records) the
+//                                  best slot_key_root4 key
+constexpr int EMINSET = 5;
+constexpr int ESUB = 10;                      // candidates per sample at the most
+constexpr int EBLOCK_RECS = RBLOCK * ESUB;    // records per hypothesis block at the most
+constexpr int EREC_DOUBLES = 10;              // (it << 4 | root) as a double's bits, E[9]
+struct EssPlan {
+  Plan base;
+  size_t cnt_off = 0, rec_off = 0, slot_off = 0, total_bytes = 0;
+};
+inline int build_plan_essential(const int32_t* set_off, int nsets, const int32_t* pairs,
+                                int npairs, int iters, EssPlan& pl) {
+  pl = EssPlan();
+  if (build_plan(set_off, nsets, pairs, npairs, iters, pl.base) != 0) return -1;
+  for (int p = 0; p < npairs; ++p) {
+    pl.base.tab[p].pad[0] = pairs[2 * p];
+    pl.base.tab[p].pad[1] = pairs[2 * p + 1];
+  }
+  const int64_t blocks = (int64_t)npairs * pl.base.nblk;
+  if (blocks * ESUB > INT32_MAX) return -1;
+  pl.cnt_off = pl.base.pts_off + align256((size_t)pl.base.total_matches * 32);
+  pl.rec_off = pl.cnt_off + align256((size_t)blocks * 4);
+  pl.slot_off = pl.rec_off + align256((size_t)blocks * EBLOCK_RECS * EREC_DOUBLES * 8);
+  pl.total_bytes = pl.slot_off + align256((size_t)blocks * ESUB * 8) + 256;
+  return 0;
+}
+
 }  // namespace pfransac_plan

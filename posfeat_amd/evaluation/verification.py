@@ -5,7 +5,7 @@ match_features and geometric_verification), without the COLMAP database.
 
   verify_pair_list(feature_dir, pairs_file, postfix, matcher="mnn", ratio=0.95,
                    model="fundamental", chunk=1024, iters=2048, thr=4.0, seed=0,
-                   output=None) -> dict
+                   output=None, intrinsics=None) -> dict
 
 ``pairs_file`` holds one ``name1 name2`` per line (image_pairs_to_match.txt);
 the features of image ``name`` are ``feature_dir/name.postfix`` as extract.py
@@ -13,7 +13,10 @@ wrote them (np.savez: keypoints, descriptors).  Per chunk of at most ``chunk``
 pairs: the images the chunk names are read once and stacked into one pool,
 matchers.match_pairs_device matches the chunk's pairs, then
 geometry.ransac_fundamental_pairs (``model="homography"``:
-ransac_homography_pairs) verifies them on the same PairBatch; counts, matches,
+ransac_homography_pairs; ``model="essential"``: ransac_essential_pairs with
+the camera of every image from ``intrinsics``, a database_intrinsics.txt as
+evaluation.reconstruction.read_intrinsics reads it) verifies them on the same
+PairBatch; counts, matches,
 models, info and masks come back in one copy with one synchronisation.  Pair p
 of a chunk samples as pair p, so the result depends on ``chunk`` through the
 chunking and on nothing else.
@@ -25,6 +28,9 @@ The returned dict, also written to ``output`` (np.savez) when given:
   model          [npairs, 3, 3] fp64 F (or H), zeros where none was found
   info           [npairs, 4] int32 as the RANSAC call gives it
   n_matches      [npairs] int32 the raw matches before verification
+and for ``model="essential"`` only:
+  pose           [npairs, 3, 4] fp64 [R | t], x2 ~ R x1 + t, |t| = 1
+  cheir          [npairs, 2] int32 (decomposition index, matches in front)
 """
 import os
 
@@ -32,9 +38,11 @@ import numpy as np
 import torch
 
 from .. import _lib, geometry, matchers
+from . import reconstruction
 
 MODELS = {"fundamental": geometry.ransac_fundamental_pairs,
-          "homography": geometry.ransac_homography_pairs}
+          "homography": geometry.ransac_homography_pairs,
+          "essential": geometry.ransac_essential_pairs}
 
 
 def read_pair_list(pairs_file):
@@ -57,8 +65,10 @@ def _read_feats(feature_dir, name, postfix):
             np.ascontiguousarray(aux["descriptors"], dtype=np.float32))
 
 
-def _run_chunk(feature_dir, postfix, names, device, matcher, ratio, fit, iters, thr, seed):
-    """names: [(name1, name2)] -> host (counts, matches [sum n1, 2], moff, model, info, mask)"""
+def _run_chunk(feature_dir, postfix, names, device, matcher, ratio, fit, iters, thr, seed,
+               cams=None):
+    """names: [(name1, name2)] -> host (counts, matches [sum n1, 2], moff, model, info, mask),
+    and with ``cams`` ({image name: camera row}, the essential model) pose and cheir"""
     images = sorted({n for pair in names for n in pair})
     index = {n: i for i, n in enumerate(images)}
     feats = [_read_feats(feature_dir, n, postfix) for n in images]
@@ -69,10 +79,16 @@ def _run_chunk(feature_dir, postfix, names, device, matcher, ratio, fit, iters, 
         raise NotImplementedError("the matcher kernel is built for 128-d descriptors")
     kp_pool = torch.from_numpy(np.concatenate([k for k, _ in feats], 0)).to(device)
     batch = matchers.match_pairs_device(pool, set_off, pairs, matcher, ratio)
-    model, info, inlier = fit(kp_pool, batch, iters=iters, thr=thr, seed=seed)
+    extra = []
+    if cams is None:
+        model, info, inlier = fit(kp_pool, batch, iters=iters, thr=thr, seed=seed)
+    else:
+        rows = torch.from_numpy(np.stack([cams[n] for n in images]).astype(np.float64)).to(device)
+        model, pose, info, cheir, inlier = fit(kp_pool, rows, batch, iters=iters, thr=thr, seed=seed)
+        extra = [pose.view(torch.uint8).view(-1), cheir.view(torch.uint8).view(-1)]
     # one synchronisation: everything into one pinned byte buffer
     parts = [batch.buf.view(torch.uint8), model.view(torch.uint8).view(-1),
-             info.view(torch.uint8).view(-1), inlier]
+             info.view(torch.uint8).view(-1), inlier] + extra
     sizes = [int(p.numel()) for p in parts]
     host = torch.empty(sum(sizes), dtype=torch.uint8, pin_memory=True)
     at = 0
@@ -83,16 +99,23 @@ def _run_chunk(feature_dir, postfix, names, device, matcher, ratio, fit, iters, 
     h = host.numpy()
     cuts = np.cumsum([0] + sizes)
     buf = h[cuts[0]:cuts[1]].view(np.int32)
-    return (buf[:npairs].copy(), buf[npairs:].reshape(-1, 2).copy(), batch.moff,
-            h[cuts[1]:cuts[2]].view(np.float64).reshape(npairs, 3, 3).copy(),
-            h[cuts[2]:cuts[3]].view(np.int32).reshape(npairs, 4).copy(),
-            h[cuts[3]:cuts[4]].astype(bool))
+    out = (buf[:npairs].copy(), buf[npairs:].reshape(-1, 2).copy(), batch.moff,
+           h[cuts[1]:cuts[2]].view(np.float64).reshape(npairs, 3, 3).copy(),
+           h[cuts[2]:cuts[3]].view(np.int32).reshape(npairs, 4).copy(),
+           h[cuts[3]:cuts[4]].astype(bool))
+    if cams is not None:
+        out += (h[cuts[4]:cuts[5]].copy().view(np.float64).reshape(npairs, 3, 4),
+                h[cuts[5]:cuts[6]].copy().view(np.int32).reshape(npairs, 2))
+    return out
 
 
 def verify_pair_list(feature_dir, pairs_file, postfix, matcher="mnn", ratio=0.95,
-                     model="fundamental", chunk=1024, iters=None, thr=None, seed=0, output=None):
+                     model="fundamental", chunk=1024, iters=None, thr=None, seed=0, output=None,
+                     intrinsics=None):
     if model not in MODELS:
         raise ValueError("model must be one of %s" % sorted(MODELS))
+    if (model == "essential") != (intrinsics is not None):
+        raise ValueError("the essential model, and no other, takes an intrinsics file")
     if matcher not in matchers._MODES:
         raise ValueError("matcher must be one of %s" % sorted(matchers._MODES))
     if int(chunk) < 1:
@@ -104,11 +127,22 @@ def verify_pair_list(feature_dir, pairs_file, postfix, matcher="mnn", ratio=0.95
     iters = fit.__defaults__[0] if iters is None else int(iters)
     thr = fit.__defaults__[1] if thr is None else float(thr)
     names = read_pair_list(pairs_file)
-    kept, offsets, models, infos, raw = [], [0], [], [], []
+    cams = None
+    if intrinsics is not None:
+        cams = {n: reconstruction.camera_row(v[0], v[3])
+                for n, v in reconstruction.read_intrinsics(intrinsics).items()}
+        missing = sorted({n for pair in names for n in pair} - set(cams))
+        if missing:
+            raise ValueError("no intrinsics for %s" % ", ".join(missing[:5]))
+    kept, offsets, models, infos, raw, poses, cheirs = [], [0], [], [], [], [], []
     for at in range(0, len(names), int(chunk)):
         part = names[at:at + int(chunk)]
-        counts, matches, moff, M, info, mask = _run_chunk(feature_dir, postfix, part, device,
-                                                          matcher, ratio, fit, iters, thr, seed)
+        got = _run_chunk(feature_dir, postfix, part, device, matcher, ratio, fit, iters, thr, seed,
+                         cams)
+        counts, matches, moff, M, info, mask = got[:6]
+        if cams is not None:
+            poses.append(got[6])
+            cheirs.append(got[7])
         for p in range(len(part)):
             rows = slice(int(moff[p]), int(moff[p]) + int(counts[p]))
             kept.append(matches[rows][mask[rows]])
@@ -124,6 +158,9 @@ def verify_pair_list(feature_dir, pairs_file, postfix, matcher="mnn", ratio=0.95
         model=np.concatenate(models, 0) if models else np.zeros((0, 3, 3)),
         info=np.concatenate(infos, 0) if infos else np.zeros((0, 4), np.int32),
         n_matches=np.concatenate(raw, 0) if raw else np.zeros(0, np.int32))
+    if cams is not None:
+        out.update(pose=np.concatenate(poses, 0) if poses else np.zeros((0, 3, 4)),
+                   cheir=np.concatenate(cheirs, 0) if cheirs else np.zeros((0, 2), np.int32))
     if output is not None:
         with open(output, "wb") as f:
             np.savez(f, **out)

@@ -1,6 +1,7 @@
-"""Robust two-view model fitting on the GPU (ransac.hip, fundamental.hip): RANSAC
-homographies or fundamental matrices for every pair of a pair list in three
-launches, on the matches matchers.match_pairs_device left on the device;
+"""Robust two-view model fitting on the GPU (ransac.hip, fundamental.hip,
+essential.hip): RANSAC homographies, fundamental matrices or five-point
+essential matrices with relative poses for every pair of a pair list in a fixed
+number of launches, on the matches matchers.match_pairs_device left on the device;
 tracks with one triangulated point each from the verified matches
 (triangulate.hip); those points refined by points-only bundle adjustment
 (refine.hip); absolute poses of queries against them (pose.hip).  The
@@ -19,9 +20,25 @@ score, selection, refit) are in include/posfeat_hip.h; no CPU path.
         distance in pixels and info[p, 3] = refit_kept | root << 8.
   find_fundamental(kp1, kp2, matches, iters=2048, thr=4.0, seed=0)
         one pair, numpy in and out: (F [3, 3], mask [m] bool, info [4]).
+  ransac_essential_pairs(kp_pool, cams, batch, iters=1024, thr=4.0, seed=0)
+        -> (E [npairs, 3, 3] fp64, pose [npairs, 3, 4] fp64, info [npairs, 4],
+        cheir [npairs, 2] int32, inlier): posfeat_ransac_essential
+        (essential.hip) between calibrated cameras, cams [nsets, 8] fp64 device
+        rows (fx, fy, cx, cy, k1, 0, 0, 0); device tensors, nothing read back.
+        pose[p] = [R | t] with x2 ~ R x1 + t, |t| = 1; cheir[p] = (decomposition
+        index, matches in front of both cameras).
+  find_essential(kp1, kp2, cam1, cam2, matches, iters=1024, thr=4.0, seed=0)
+        one pair, numpy in and out: (E [3, 3], pose [3, 4], mask [m] bool,
+        info [4]).
+  solve5(m)
+        the five-point candidates [c, 3, 3] (c = 0..10) of five matches m [5, 4]
+        in normalised camera coordinates (host only, needs no device).
+  decompose_essential(E, m)
+        (pose [3, 4], decomposition index, n_front) of E over the matches m
+        [n, 4] in normalised camera coordinates (host only, needs no device).
   sample_indices(seed, pair, it, n, k=4)
-        the first k match indices (4 for a homography, 7 for a fundamental
-        matrix) iteration ``it`` of pair ``pair`` draws from ``n`` matches (host
+        the first k match indices (4 for a homography, 5 for an essential, 7
+        for a fundamental matrix) iteration ``it`` of pair ``pair`` draws from ``n`` matches (host
         only, needs no device).
   solve7(m)
         the 7-point candidates [c, 3, 3] (c = 0..3) of seven matches m [7, 4] in
@@ -100,6 +117,40 @@ def solve7(m):
     return out[:c]
 
 
+def solve5(m):
+    """posfeat_essential_solve5: m [5, 4] rows (x, y, u, v) in normalised camera
+    coordinates -> the candidates [c, 3, 3], unit norm, largest entry positive;
+    c = 0 for a rejected sample."""
+    m = np.ascontiguousarray(m, dtype=np.float64)
+    if m.shape != (5, 4):
+        raise ValueError("solve5 takes five (x, y, u, v) rows")
+    out = np.zeros((10, 3, 3), dtype=np.float64)
+    c = lib().posfeat_essential_solve5(ctypes.c_void_p(m.ctypes.data),
+                                       ctypes.c_void_p(out.ctypes.data))
+    if c < 0:
+        raise ValueError("posfeat_essential_solve5 failed (%d)" % c)
+    return out[:c]
+
+
+def decompose_essential(E, m):
+    """posfeat_essential_decompose: E [3, 3] and the matches m [n, 4] in
+    normalised camera coordinates -> (pose [3, 4] = [R | t], the index of the
+    chosen decomposition, the matches in front of both cameras)."""
+    E = np.ascontiguousarray(E, dtype=np.float64)
+    m = np.ascontiguousarray(m, dtype=np.float64)
+    if E.shape != (3, 3) or m.ndim != 2 or m.shape[1] != 4:
+        raise ValueError("decompose_essential takes E [3, 3] and (x, y, u, v) rows")
+    pose = np.zeros((3, 4), dtype=np.float64)
+    front = np.zeros(2, dtype=np.int32)
+    r = lib().posfeat_essential_decompose(ctypes.c_void_p(E.ctypes.data),
+                                          ctypes.c_void_p(m.ctypes.data) if m.shape[0] else None,
+                                          int(m.shape[0]), ctypes.c_void_p(pose.ctypes.data),
+                                          ctypes.c_void_p(front.ctypes.data))
+    if r != 0:
+        raise ValueError("E has no finite decomposition")
+    return pose, int(front[0]), int(front[1])
+
+
 def _ransac_pairs(model, kp_pool, batch, iters, thr, seed):
     """the one call shape both models share"""
     _lib.require_device(kp_pool)
@@ -138,6 +189,84 @@ def ransac_fundamental_pairs(kp_pool, batch, iters=2048, thr=4.0, seed=0):
     the arguments of ransac_homography_pairs.  thr = 4 px is COLMAP's two-view
     max_error default."""
     return _ransac_pairs("fundamental", kp_pool, batch, iters, thr, seed)
+
+
+def ransac_essential_pairs(kp_pool, cams, batch, iters=1024, thr=4.0, seed=0):
+    """posfeat_ransac_essential on what ``batch`` (matchers.PairBatch) holds;
+    kp_pool as for ransac_homography_pairs, cams [nsets, 8] fp64 device tensor,
+    one camera row per set.  thr is in pixels (COLMAP's two-view default)."""
+    _lib.require_device(kp_pool)
+    if kp_pool.dtype != torch.float32 or kp_pool.dim() != 2 or kp_pool.shape[1] != 2:
+        raise ValueError("kp_pool must be a [N, 2] float32 tensor")
+    kp_pool = kp_pool.contiguous()
+    set_off, pairs = batch.set_off, batch.pairs
+    npairs, nsets = pairs.shape[0], set_off.shape[0] - 1
+    if kp_pool.shape[0] < int(set_off[-1]):
+        raise ValueError("kp_pool has fewer rows than the sets of the batch")
+    if (not torch.is_tensor(cams) or cams.dtype != torch.float64 or cams.dim() != 2 or
+            tuple(cams.shape) != (nsets, 8) or cams.device != kp_pool.device):
+        raise ValueError("cams must be a [nsets, 8] float64 tensor on kp_pool's device")
+    cams = cams.contiguous()
+    so, pp = ctypes.c_void_p(set_off.ctypes.data), ctypes.c_void_p(pairs.ctypes.data)
+    need = lib().posfeat_ransac_essential_workspace(so, nsets, pp, npairs, int(iters))
+    if need == 0:
+        raise ValueError("invalid pair tables, or iters outside 1..65536")
+    dev = kp_pool.device
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    E = torch.empty(npairs, 3, 3, dtype=torch.float64, device=dev)
+    pose = torch.empty(npairs, 3, 4, dtype=torch.float64, device=dev)
+    info = torch.empty(npairs, 4, dtype=torch.int32, device=dev)
+    cheir = torch.empty(npairs, 2, dtype=torch.int32, device=dev)
+    inlier = torch.empty(int(batch.moff[-1]), dtype=torch.uint8, device=dev)
+    check(lib().posfeat_ransac_essential(
+        ptr(kp_pool), ptr(cams), so, nsets, pp, npairs, ptr(batch.matches), ptr(batch.counts),
+        int(iters), float(thr), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(E), ptr(pose), ptr(info),
+        ptr(cheir), ptr(inlier), ptr(ws), need, stream_ptr(dev)))
+    return E, pose, info, cheir, inlier
+
+
+def _one_pair(kp1, kp2, matches, dev):
+    """the two-set pool and the one-pair batch of find_*: (kp_pool, batch, m),
+    or None when the first set is empty"""
+    kp1 = np.ascontiguousarray(np.asarray(kp1)[:, :2], dtype=np.float32)
+    kp2 = np.ascontiguousarray(np.asarray(kp2)[:, :2], dtype=np.float32)
+    matches = np.asarray(matches, dtype=np.int32).reshape(-1, 2)
+    n1, m = kp1.shape[0], matches.shape[0]
+    if m > n1:
+        raise ValueError("more matches (%d) than keypoints in the first set (%d)" % (m, n1))
+    if n1 == 0:
+        return None
+    set_off = np.asarray([0, n1, n1 + kp2.shape[0]], dtype=np.int32)
+    pairs = np.asarray([[0, 1]], dtype=np.int32)
+    rows = np.full((n1, 2), -1, np.int32)
+    rows[:m] = matches
+    buf = torch.from_numpy(np.concatenate([[m], rows.reshape(-1)]).astype(np.int32)).to(dev)
+    batch = matchers.PairBatch(None, set_off, pairs, np.asarray([0, n1]), buf)
+    return torch.from_numpy(np.concatenate([kp1, kp2], 0)).to(dev), batch, m
+
+
+def find_essential(kp1, kp2, cam1, cam2, matches, iters=1024, thr=4.0, seed=0):
+    """find_fundamental's counterpart between two calibrated cameras: cam1, cam2
+    are camera rows (fx, fy, cx, cy, k1, 0, 0, 0).  Returns (E [3, 3] fp64 with
+    Frobenius norm 1, pose [3, 4] = [R | t], mask [m] bool, info [4] int32); E
+    and pose are all zeros and info[0] = 1 when no model was found."""
+    _lib.require_device()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    cams = np.zeros((2, 8), np.float64)
+    for row, cam in zip(cams, (cam1, cam2)):
+        cam = np.asarray(cam, np.float64).reshape(-1)
+        if cam.shape[0] < 4 or cam.shape[0] > 8:
+            raise ValueError("a camera row is (fx, fy, cx, cy[, k1, 0, 0, 0])")
+        row[:cam.shape[0]] = cam
+    one = _one_pair(kp1, kp2, matches, dev)
+    if one is None:
+        return (np.zeros((3, 3)), np.zeros((3, 4)), np.zeros(0, bool),
+                np.asarray([1, 0, -1, 0], np.int32))
+    kp_pool, batch, m = one
+    E, pose, info, _, inlier = ransac_essential_pairs(kp_pool, torch.from_numpy(cams).to(dev),
+                                                      batch, iters, thr, seed)
+    return (E[0].cpu().numpy(), pose[0].cpu().numpy(), inlier[:m].cpu().numpy().astype(bool),
+            info[0].cpu().numpy())
 
 
 def _find(model, kp1, kp2, matches, iters, thr, seed):
