@@ -255,7 +255,12 @@ int posfeat_normalize_rgb8(const unsigned char *src, int b, int h, int w, int sr
  * xf1/xf2: NHWC local maps [b][H/4][W/4] (128 channels, pixel stride cs).
  * F1/F2: [b][3][3].  sel1/sel2: [b][n] Categorical draw (0..grid^2-1) per
  * grid cell; rand1/rand2: [b][n][2] U(0,1) (loc_rand jitter).  The caller owns
- * the RNG; n = (H/grid)*(W/grid).  Outputs (caller buffers, [b][n][...]):
+ * the RNG; n = (H/grid)*(W/grid) per image (n1 for image 1, n2 for image 2).
+ * Limits: H, W multiples of 4; 2 <= line_step <= 128 (POSFEAT_E_INVALID);
+ * n2 % 4 == 0 and 1 <= (int)(window_size * H/4) * (int)(window_size * W/4) <=
+ * 512 window taps per image with both factors >= 1 (POSFEAT_E_UNSUPPORTED).
+ * Every refusal is made before any output is written.
+ * Outputs (caller buffers, [b][n][...]):
  * ------------------------------------------------------------------------ */
 typedef struct {
   float *coord1, *coord2;       /* grid points, pixels [b][n][2]             */
@@ -275,8 +280,11 @@ int posfeat_line2window(const float *xf1, int cs1, const float *xf2, int cs2, in
                         const float *rand2, float temperature, int grid, float window_size,
                         int line_step, posfeat_l2w_out *out, void *ws, size_t ws_bytes,
                         void *stream);
-/* out[7] = {loss, loss_g1, loss_w1, loss_g2, loss_w2, percent_g, percent_w} */
-int posfeat_epipolar_loss(int b, int n, const float *F1, const float *F2, const float *c1,
+/* out[7] = {loss, loss_g1, loss_w1, loss_g2, loss_w2, percent_g, percent_w}.
+ * n1 / n2: points per image of side 1 (c1, g1, w1, sg1, sw1, v1) and of side 2
+ * (c2, g2, w2, sg2, sw2, v2); they differ when the two images differ in size.
+ * Every mean is over its own side's b * n points. */
+int posfeat_epipolar_loss(int b, int n1, int n2, const float *F1, const float *F2, const float *c1,
                           const float *c2, const float *g1, const float *g2, const float *w1,
                           const float *w2, const float *sg1, const float *sg2, const float *sw1,
                           const float *sw2, const uint8_t *v1, const uint8_t *v2,

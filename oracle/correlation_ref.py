@@ -1,7 +1,9 @@
 """torch-CPU restatement of the training-side descriptor correlation
-(TEST ORACLE), fp32 as the reference runs it; the DiskLoss part follows the
-dtype of the maps passed in (float64 maps give the fp64 reference of
-tests/disk_fixture.py).  Random draws are explicit inputs so the same values can be
+(TEST ORACLE), fp32 as the reference runs it.  Every function follows the
+dtype of the maps / coordinates passed in: float64 inputs give the fp64
+references of tests/disk_fixture.py and tests/line2window_fixture.py (grids and
+linspaces are then built in float64 too); float32 inputs give the reference's
+own arithmetic.  Random draws are explicit inputs so the same values can be
 fed to the HIP kernels:
 
 * ``grid_points``            generate_kpts_regular_grid_random(_single),
@@ -22,10 +24,10 @@ import torch
 import torch.nn.functional as F
 
 
-def gen_grid(h_min, h_max, w_min, w_max, len_h, len_w):
-    y, x = torch.meshgrid(torch.linspace(h_min, h_max, len_h), torch.linspace(w_min, w_max, len_w),
-                          indexing="ij")
-    return torch.stack((x, y), -1).reshape(-1, 2).float()
+def gen_grid(h_min, h_max, w_min, w_max, len_h, len_w, dtype=torch.float32):
+    y, x = torch.meshgrid(torch.linspace(h_min, h_max, len_h, dtype=dtype),
+                          torch.linspace(w_min, w_max, len_w, dtype=dtype), indexing="ij")
+    return torch.stack((x, y), -1).reshape(-1, 2)
 
 
 def normalize_coords(coord, h, w):
@@ -34,7 +36,7 @@ def normalize_coords(coord, h, w):
 
 
 def denormalize_coords(coord_n, h, w):
-    c = torch.tensor([(w - 1) / 2.0, (h - 1) / 2.0], dtype=torch.float32)
+    c = torch.tensor([(w - 1) / 2.0, (h - 1) / 2.0], dtype=coord_n.dtype)
     return coord_n * c + c
 
 
@@ -49,11 +51,11 @@ def sample_feat(x, coord_n, norm):
     return f.transpose(1, 2)
 
 
-def grid_points(sel, h, w, g):
+def grid_points(sel, h, w, g, dtype=torch.float32):
     """sel: [b, h//g, w//g] int in [0, g*g) -> normalised coords [b, (h//g)*(w//g), 2]."""
     b, hc, wc = sel.shape
-    xs = torch.linspace(-1, 1, w)
-    ys = torch.linspace(-1, 1, h)
+    xs = torch.linspace(-1, 1, w, dtype=dtype)
+    ys = torch.linspace(-1, 1, h, dtype=dtype)
     ry, rx = sel // g, sel % g
     iy = torch.arange(hc).view(1, hc, 1) * g + ry
     ix = torch.arange(wc).view(1, 1, wc) * g + rx
@@ -82,14 +84,14 @@ def epipolar_line_search(coord, Fmat, feat1, featmap2, h, w, rand, line_step=100
     b, n = coord.shape[:2]
     d = featmap2.shape[1]
     e1, e2, valid = get_endpoints(coord, Fmat, h, w)
-    t = torch.stack([torch.linspace(0.0, 1.0, line_step)] * 2, -1)
+    t = torch.stack([torch.linspace(0.0, 1.0, line_step, dtype=coord.dtype)] * 2, -1)
     grids = (e2 - e1)[:, :, None, :] * t[None, None] + e1[:, :, None, :]
     pts = F.grid_sample(featmap2, grids, padding_mode="border", align_corners=False).permute(0, 2, 3, 1)
     sim = feat1.reshape(b * n, 1, d).bmm(pts.reshape(b * n, line_step, d).transpose(1, 2))
     prob = F.softmax(sim, dim=-1).reshape(b, n, line_step)
     mask = prob == prob.max(-1, True)[0]
     exp_org = (mask.unsqueeze(-1) * grids).sum(2)
-    expected = exp_org + 0.707 * window_size * (2 * rand - 1)
+    expected = exp_org + 0.707 * window_size * (2 * rand.to(exp_org.dtype) - 1)
     border = (expected[:, :, 0] >= -1) & (expected[:, :, 0] <= 1) & (expected[:, :, 1] >= -1) & \
         (expected[:, :, 1] <= 1)
     valid = valid & border
@@ -102,7 +104,7 @@ def window_expectation(feat1, featmap2, center_n, window_size):
     b, d, h2, w2 = featmap2.shape
     n = center_n.shape[1]
     grid_n = gen_grid(-window_size, window_size, -window_size, window_size,
-                      int(window_size * h2), int(window_size * w2))
+                      int(window_size * h2), int(window_size * w2), dtype=center_n.dtype)
     g = center_n.unsqueeze(-2) + grid_n.view(1, 1, -1, 2)
     win = F.grid_sample(featmap2, g, padding_mode="zeros", align_corners=False).permute(0, 2, 3, 1)
     sim = feat1.reshape(b * n, 1, d).bmm(win.reshape(b * n, -1, d).transpose(1, 2))
@@ -120,8 +122,8 @@ def line2window(xf1, xf2, F1, F2, im_hw1, im_hw2, sel1, sel2, rand1, rand2, temp
     h1i, w1i = im_hw1
     h2i, w2i = im_hw2
     b = xf1.shape[0]
-    c1n = grid_points(sel1, h1i, w1i, grid_size)
-    c2n = grid_points(sel2, h2i, w2i, grid_size)
+    c1n = grid_points(sel1, h1i, w1i, grid_size, xf1.dtype)
+    c2n = grid_points(sel2, h2i, w2i, grid_size, xf2.dtype)
     coord1 = denormalize_coords(c1n, h1i, w1i)
     coord2 = denormalize_coords(c2n, h2i, w2i)
     f1 = sample_feat(xf1, c1n, True)

@@ -23,12 +23,14 @@ def desc_loss_grad(xf1, xf2, F1, F2, hw1, hw2, sel1, sel2, rand1, rand2, tempera
     centres to use instead of this function's own line search (so a test can
     share the GPU's arg-max on near-ties); their validity is re-derived as the
     reference does (endpoints valid & centre inside the image).  ``weights`` =
-    the two detached per-point loss weights (see loss_weights) to use as given."""
+    the two detached per-point loss weights (see loss_weights) to use as given.
+    Runs in the dtype of the maps (float64 maps, matrices and centres: the fp64
+    reference of tests/line2window_fixture.py)."""
     (h1i, w1i), (h2i, w2i) = hw1, hw2
     xf1 = xf1.detach().clone().requires_grad_(True)
     xf2 = xf2.detach().clone().requires_grad_(True)
-    c1n = grid_points(sel1, h1i, w1i, grid_size)
-    c2n = grid_points(sel2, h2i, w2i, grid_size)
+    c1n = grid_points(sel1, h1i, w1i, grid_size, xf1.dtype)
+    c2n = grid_points(sel2, h2i, w2i, grid_size, xf2.dtype)
     coord1 = denormalize_coords(c1n, h1i, w1i)
     coord2 = denormalize_coords(c2n, h2i, w2i)
     f1 = sample_feat(xf1, c1n, True)

@@ -101,7 +101,7 @@ SIGNATURES = {
                                     c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_float, c_int, c_float, c_int,
                                     ctypes.POINTER(L2WOut), c_void_p, c_size_t, c_void_p]),
-    "posfeat_epipolar_loss": (c_int, [c_int, c_int] + [c_void_p] * 14 + [c_float] * 5 +
+    "posfeat_epipolar_loss": (c_int, [c_int, c_int, c_int] + [c_void_p] * 14 + [c_float] * 5 +
                               [c_void_p, c_void_p]),
     "posfeat_disk_loss_workspace": (c_size_t, [c_int, c_int, c_int]),
     "posfeat_disk_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,

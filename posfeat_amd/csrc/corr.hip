@@ -584,16 +584,17 @@ __device__ __forceinline__ float epi_cost(const float* F, float x1, float y1, fl
 }
 
 // EpipolarLoss_full.forward: one workgroup.  out[0] = loss, out[1..6] =
-// loss_g1, loss_w1, loss_g2, loss_w2, percent_g, percent_w.
+// loss_g1, loss_w1, loss_g2, loss_w2, percent_g, percent_w.  Sets 0 and 1
+// (g1, w1) hold n1 points per image, sets 2 and 3 (g2, w2) hold n2: each set's
+// means are over its own count.
 __global__ __launch_bounds__(1024) PF_NO_PK_FP32 void epipolar_loss_kernel(
-    int nb, int n, const float* __restrict__ F1, const float* __restrict__ F2,
+    int nb, int n1, int n2, const float* __restrict__ F1, const float* __restrict__ F2,
     const float* __restrict__ c1, const float* __restrict__ c2, const float* __restrict__ g1,
     const float* __restrict__ g2, const float* __restrict__ w1, const float* __restrict__ w2,
     const float* __restrict__ sg1, const float* __restrict__ sg2, const float* __restrict__ sw1,
     const float* __restrict__ sw2, const uint8_t* __restrict__ v1, const uint8_t* __restrict__ v2,
     float short_edge, float gthr, float wthr, float wg, float ww, float* __restrict__ out) {
   const int tid = threadIdx.x;
-  const int total = nb * n;
   // one pass per set: with inv_i = 1 / std_i and m_i the mask, the weights
   // w_i = m_i inv_i / mean(inv) give sum w = S / mean(inv) and sum w cost =
   // C / mean(inv), S = sum m_i inv_i, C = sum m_i inv_i cost_i -- the same
@@ -603,6 +604,7 @@ __global__ __launch_bounds__(1024) PF_NO_PK_FP32 void epipolar_loss_kernel(
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     double a1 = 0.0, a2 = 0.0, sm = 0.0, cm = 0.0;
+    const int n = k < 2 ? n1 : n2, total = nb * n;
     for (int i = tid; i < total; i += blockDim.x) {
       const int b = i / n;
       const float* F = (k < 2 ? F1 : F2) + b * 9;
@@ -645,6 +647,7 @@ __global__ __launch_bounds__(1024) PF_NO_PK_FP32 void epipolar_loss_kernel(
       sm += red[wv][k * 4 + 2];
       cm += red[wv][k * 4 + 3];
     }
+    const int total = nb * (k < 2 ? n1 : n2);
     const double inv_mean = a1 / total;
     const double wmean = sm / inv_mean / total + 1e-8;
     lsum[k] = cm / inv_mean / wmean / total;
@@ -1300,8 +1303,11 @@ extern "C" int posfeat_line2window(const float* xf1, int cs1, const float* xf2, 
   if (win_h2 * win_w2 > MAX_WIN || win_h1 * win_w1 > MAX_WIN || win_h1 < 1 || win_w1 < 1 ||
       win_h2 < 1 || win_w2 < 1)
     return POSFEAT_E_UNSUPPORTED;
-  if (ws_bytes < posfeat_line2window_workspace(b, H1, W1, H2, W2, grid)) return POSFEAT_E_WORKSPACE;
   const int n1 = (H1 / grid) * (W1 / grid), n2 = (H2 / grid) * (W2 / grid);
+  // S = f1 f2^T runs on the conv engine with cout = n2 (16-B output rows);
+  // refused here, before anything is written
+  if (n1 <= 0 || n2 <= 0 || n2 % 4 != 0) return POSFEAT_E_UNSUPPORTED;
+  if (ws_bytes < posfeat_line2window_workspace(b, H1, W1, H2, W2, grid)) return POSFEAT_E_WORKSPACE;
   hipStream_t st = pf_stream(stream);
   const L2WLayout lay = l2w_layout(b, H1, W1, H2, W2, grid);
   char* wb = static_cast<char*>(ws);
@@ -1337,25 +1343,21 @@ extern "C" int posfeat_line2window(const float* xf1, int cs1, const float* xf2, 
                      dim3(256), 0, st, xf2, (long long)b * h2 * w2, cs2, temperature, fm2);
   PF_CHECK_LAUNCH();
   // S = f1 f2^T per pair on the MFMA conv engine (1x1 conv, weights = f2)
-  if (n2 % 4 == 0) {
-    for (int i = 0; i < b; ++i) {
-      posfeat_conv_desc d;
-      d.n = 1;
-      d.h = 1;
-      d.w = n1;
-      d.cin = 128;
-      d.x_cstride = 128;
-      d.cout = n2;
-      d.kh = d.kw = d.stride = 1;
-      d.pad = 0;
-      d.y_cstride = n2;
-      d.res_cstride = 0;
-      d.act = POSFEAT_ACT_NONE;
-      PF_TRY(posfeat_conv2d_nhwc(&d, f1 + (size_t)i * n1 * 128, f2 + (size_t)i * n2 * 128, nullptr,
-                                 nullptr, S + (size_t)i * n1 * n2, st));
-    }
-  } else {
-    return POSFEAT_E_UNSUPPORTED;
+  for (int i = 0; i < b; ++i) {
+    posfeat_conv_desc d;
+    d.n = 1;
+    d.h = 1;
+    d.w = n1;
+    d.cin = 128;
+    d.x_cstride = 128;
+    d.cout = n2;
+    d.kh = d.kw = d.stride = 1;
+    d.pad = 0;
+    d.y_cstride = n2;
+    d.res_cstride = 0;
+    d.act = POSFEAT_ACT_NONE;
+    PF_TRY(posfeat_conv2d_nhwc(&d, f1 + (size_t)i * n1 * 128, f2 + (size_t)i * n2 * 128, nullptr,
+                               nullptr, S + (size_t)i * n1 * n2, st));
   }
   hipLaunchKernelGGL(corr_row_kernel, dim3((b * n1 + 3) / 4), dim3(256), 0, st, S, b, n1, n2,
                      temperature, c2p, c2n, H2, W2, out->g1, out->g1_std);
@@ -1379,7 +1381,7 @@ extern "C" int posfeat_line2window(const float* xf1, int cs1, const float* xf2, 
   return POSFEAT_OK;
 }
 
-extern "C" int posfeat_epipolar_loss(int b, int n, const float* F1, const float* F2,
+extern "C" int posfeat_epipolar_loss(int b, int n1, int n2, const float* F1, const float* F2,
                                      const float* c1, const float* c2, const float* g1,
                                      const float* g2, const float* w1, const float* w2,
                                      const float* sg1, const float* sg2, const float* sw1,
@@ -1387,10 +1389,10 @@ extern "C" int posfeat_epipolar_loss(int b, int n, const float* F1, const float*
                                      float short_edge, float grid_thr, float win_thr,
                                      float weight_grid, float weight_window, float* out,
                                      void* stream) {
-  if (b <= 0 || n <= 0 || !out) return POSFEAT_E_INVALID;
-  hipLaunchKernelGGL(epipolar_loss_kernel, dim3(1), dim3(1024), 0, pf_stream(stream), b, n, F1,
-                     F2, c1, c2, g1, g2, w1, w2, sg1, sg2, sw1, sw2, v1, v2, short_edge, grid_thr,
-                     win_thr, weight_grid, weight_window, out);
+  if (b <= 0 || n1 <= 0 || n2 <= 0 || !out) return POSFEAT_E_INVALID;
+  hipLaunchKernelGGL(epipolar_loss_kernel, dim3(1), dim3(1024), 0, pf_stream(stream), b, n1, n2,
+                     F1, F2, c1, c2, g1, g2, w1, w2, sg1, sg2, sw1, sw2, v1, v2, short_edge,
+                     grid_thr, win_thr, weight_grid, weight_window, out);
   PF_CHECK_LAUNCH();
   return POSFEAT_OK;
 }

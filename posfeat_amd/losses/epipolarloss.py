@@ -28,9 +28,8 @@ class EpipolarLoss_full(nn.Module):
 
     def forward(self, inputs, outputs, processed):
         p = processed
-        b, n = p["coord1"].shape[:2]
-        if p["coord2"].shape[1] != n:
-            raise NotImplementedError("both images must have the same grid size")
+        b, n1 = p["coord1"].shape[:2]
+        n2 = p["coord2"].shape[1]
         dev = p["coord1"].device
         F1 = inputs["F1"].to(dev).float().contiguous()
         F2 = inputs["F2"].to(dev).float().contiguous()
@@ -42,7 +41,7 @@ class EpipolarLoss_full(nn.Module):
         args = [c("coord1"), c("coord2"), c("feat1g_corloc"), c("feat2g_corloc"),
                 c("feat1w_corloc"), c("feat2w_corloc"), c("feat1g_std"), c("feat2g_std"),
                 c("feat1w_std"), c("feat2w_std")]
-        check(lib().posfeat_epipolar_loss(b, n, ptr(F1), ptr(F2), *[ptr(a) for a in args],
+        check(lib().posfeat_epipolar_loss(b, n1, n2, ptr(F1), ptr(F2), *[ptr(a) for a in args],
                                           ptr(v1), ptr(v2), short,
                                           float(self.config["grid_cost_thr"]),
                                           float(self.config["win_cost_thr"]), float(self.w_g),

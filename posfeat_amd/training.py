@@ -203,7 +203,7 @@ class DescriptorLossGrad:
         short = float(min(H1, W1))
         args = [res[k] for k in ("coord1", "coord2", "g1", "g2", "w1", "w2", "g1_std", "g2_std",
                                  "w1_std", "w2_std")]
-        check(L.posfeat_epipolar_loss(b, n1, ptr(F1), ptr(F2), *[ptr(a) for a in args],
+        check(L.posfeat_epipolar_loss(b, n1, n2, ptr(F1), ptr(F2), *[ptr(a) for a in args],
                                       ptr(res["valid1"]), ptr(res["valid2"]), short,
                                       float(self.epi["grid_cost_thr"]),
                                       float(self.epi["win_cost_thr"]),

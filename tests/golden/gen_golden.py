@@ -372,6 +372,70 @@ def gen_desc_grad(out):
     np.savez_compressed(out, **res)
 
 
+DESC_GRAD_EDGE_CASES = ("uneq", "g8")
+
+
+def gen_desc_grad_edges(out):
+    """gen_desc_grad on two cases of tests/line2window_fixture.py: ``uneq``
+    (b = 2, 160x224 / 128x192: n1 != n2, the reference takes one mean per
+    direction) and ``g8`` (grid 8).  Maps and F from the fixture, the draws the
+    reference's own (replayed); holds the draws, the loss and its components,
+    the jittered line centres, the window expectations and both map gradients
+    at every second pixel in each direction of every second channel, with
+    full-map sums."""
+    import line2window_fixture as LF
+    res = {}
+    for tag in DESC_GRAD_EDGE_CASES:
+        spec = LF.CASES[tag]
+        inp = LF.raw_inputs(spec)
+        b, g, seed = spec["b"], spec["grid"], spec["seed"]
+        (H1, W1), (H2, W2) = spec["hw1"], spec["hw2"]
+        cfg = dict(DESC_CFG, window_size=spec["window"],
+                   kps_generator_config=dict(DESC_CFG["kps_generator_config"], grid_size=g),
+                   line_search_config=dict(DESC_CFG["line_search_config"],
+                                           line_step=spec["line_step"]))
+        xf1 = inp["xf1"].clone().requires_grad_(True)
+        xf2 = inp["xf2"].clone().requires_grad_(True)
+        inputs = {"im1": torch.zeros(b, 3, H1, W1), "im2": torch.zeros(b, 3, H2, W2),
+                  "F1": inp["F1"], "F2": inp["F2"]}
+        outputs = {"preds1": {"global_map": xf1[:, :, ::4, ::4], "local_map": xf1,
+                              "local_point": torch.zeros(b, 1, H1, W1)},
+                   "preds2": {"global_map": xf2[:, :, ::4, ::4], "local_map": xf2,
+                              "local_point": torch.zeros(b, 1, H2, W2)}, "epoch": 0}
+        pre = ref_losses.Preprocess_Line2Window(cfg)
+        torch.manual_seed(100 + seed)
+        proc = pre(inputs, outputs)
+        loss, comp = ref_losses.EpipolarLoss_full(EPI_CFG)(inputs, outputs, proc)
+        loss.backward()
+        torch.manual_seed(100 + seed)
+        k1, k2, _, _ = ref_putils.generate_kpts_regular_grid_random(
+            inputs, outputs, **cfg["kps_generator_config"])
+        r1 = torch.rand(b, k1.shape[1] * k1.shape[2], 2)
+        r2 = torch.rand(b, k2.shape[1] * k2.shape[2], 2)
+        for name, k, hh, ww in (("sel1", k1, H1, W1), ("sel2", k2, H2, W2)):
+            ix = torch.round((k[..., 0] + 1) / 2 * (ww - 1)).long()
+            iy = torch.round((k[..., 1] + 1) / 2 * (hh - 1)).long()
+            res["%s_%s" % (tag, name)] = ((iy % g) * g + ix % g).int().numpy()
+        res[tag + "_rand1"] = r1.numpy()
+        res[tag + "_rand2"] = r2.numpy()
+        res[tag + "_loss"] = loss.detach().numpy()
+        for k, v in comp.items():
+            res["%s_%s" % (tag, k)] = v.detach().numpy()
+        # the line arg-max centres before the jitter (the jitter is 0.707 window (2 rand - 1))
+        res[tag + "_l1_org"] = proc["feat1c_corloc_org"].detach().numpy()   # pixels (image 2)
+        res[tag + "_l2_org"] = proc["feat2c_corloc_org"].detach().numpy()   # normalised (sic)
+        res[tag + "_w1"] = proc["feat1w_corloc"].detach().numpy()
+        res[tag + "_w2"] = proc["feat2w_corloc"].detach().numpy()
+        # every second pixel in each direction of every second channel (all
+        # channels would put the file over the 1 MiB limit) + full-map sums
+        g1, g2 = xf1.grad.numpy(), xf2.grad.numpy()
+        res[tag + "_dxf1_sub"] = g1[:, ::2, ::2, ::2]
+        res[tag + "_dxf2_sub"] = g2[:, ::2, ::2, ::2]
+        res[tag + "_dxf_sums"] = np.array([g1.astype(np.float64).sum(), np.abs(g1).sum(),
+                                           g2.astype(np.float64).sum(), np.abs(g2).sum()])
+    np.savez_compressed(out, **res)
+
+
 TRAIN_KP_CASES ={"a": (2, 64, 96, 5, 300), "b": (1, 96, 128, 6, 301)}
 
 
@@ -528,6 +592,8 @@ if __name__ == "__main__":
         gen_train_kp(os.path.join(HERE, "train_kp.npz"))
     if "desc_grad" in which:
         gen_desc_grad(os.path.join(HERE, "desc_grad.npz"))
+    if "desc_grad_edges" in which:
+        gen_desc_grad_edges(os.path.join(HERE, "desc_grad_edges.npz"))
     if "bb_grad" in which:
         gen_bb_grad(os.path.join(HERE, "bb_grad.npz"))
     if "detector" in which:

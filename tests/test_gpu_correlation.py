@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN
+from line2window_fixture import _fp64_reference_stage
 
 pytestmark = pytest.mark.gpu
 
@@ -83,46 +84,6 @@ def test_line2window_vs_reference(gpu, tag):
         np.testing.assert_allclose(loss.item(), float(d[tag + "_epi_loss"]), rtol=1e-3)
         for k, v in comp.items():
             np.testing.assert_allclose(v.item(), float(d["%s_epi_%s" % (tag, k)]), rtol=1e-3)
-
-
-def _fp64_reference_stage(tag, d, raw):
-    """The reference's formulas (oracle/correlation_ref.py, which the fp32
-    goldens pin) evaluated in float64 on the same inputs and draws, with the
-    window stage centred on the GPU's own jittered line expectations (the
-    discrete line arg-max is compared separately)."""
-    from oracle import correlation_ref as cr
-    from test_oracle_correlation import _inputs
-    b, H, W, xf1, xf2, kp1, kp2, F1, F2 = _inputs(tag)
-    xf1, xf2, F1, F2 = xf1.double(), xf2.double(), F1.double(), F2.double()
-    sel1 = torch.from_numpy(d[tag + "_sel1"]).long()
-    sel2 = torch.from_numpy(d[tag + "_sel2"]).long()
-    c1n = cr.grid_points(sel1, H, W, 16).double()
-    c2n = cr.grid_points(sel2, H, W, 16).double()
-    half = torch.tensor([(W - 1) / 2.0, (H - 1) / 2.0], dtype=torch.float64)
-    coord1, coord2 = c1n * half + half, c2n * half + half
-    f1 = cr.sample_feat(xf1, c1n, True)
-    f2 = cr.sample_feat(xf2, c2n, True)
-    T = 60.0
-    cos = f1 @ f2.transpose(1, 2)
-    p_row = torch.softmax(T * cos, dim=2)
-    p_col = torch.softmax(T * cos, dim=1)
-    g1 = (p_row.unsqueeze(-1) * coord2.unsqueeze(1)).sum(2)
-    g2 = (p_col.unsqueeze(-1) * coord1.unsqueeze(2)).sum(1)
-    s1 = ((p_row.unsqueeze(-1) * (c2n.reshape(b, 1, -1, 2) ** 2)).sum(2) - ((g1 - half) / half) ** 2)
-    s2 = ((p_col.unsqueeze(-1) * (c1n.reshape(b, -1, 1, 2) ** 2)).sum(1) - ((g2 - half) / half) ** 2)
-    s1 = s1.clamp(min=1e-6).sqrt().sum(-1)
-    s2 = s2.clamp(min=1e-6).sqrt().sum(-1)
-    fm1 = T * torch.nn.functional.normalize(xf1, p=2.0, dim=1)
-    fm2 = T * torch.nn.functional.normalize(xf2, p=2.0, dim=1)
-    l1 = raw["l1_exp_n"].cpu().double()
-    l2 = raw["l2_exp_n"].cpu().double()
-    w1n, _, w1s = cr.window_expectation(f1, fm2, l1, 0.1)
-    w2n, _, w2s = cr.window_expectation(f2, fm1, l2, 0.1)
-    proc = {"coord1": coord1, "coord2": coord2, "feat1g_corloc": g1, "feat2g_corloc": g2,
-            "feat1w_corloc": w1n * half + half, "feat2w_corloc": w2n * half + half,
-            "feat1g_std": s1, "feat2g_std": s2, "feat1w_std": w1s, "feat2w_std": w2s,
-            "valid_epi1": raw["valid1"].cpu().bool(), "valid_epi2": raw["valid2"].cpu().bool()}
-    return proc, F1, F2, (H, W), half.numpy()
 
 
 @pytest.mark.parametrize("tag", ["s", "f"])
