@@ -682,6 +682,79 @@ int posfeat_match_pairs(const float *desc, const int32_t *set_off, int nsets, co
                         int npairs, int dim, int mode, float ratio, int32_t *matches,
                         int32_t *counts, void *ws, size_t ws_bytes, void *stream);
 
+/* Guided matching: posfeat_match_pairs with the candidates of every pair
+ * restricted by the pair's verified two-view model (what COLMAP's guided
+ * matching does after two-view geometry; the reference hands this to COLMAP).
+ * desc, set_off, nsets, pairs, npairs, dim, mode, ratio, matches, counts, ws
+ * and stream mean what they mean for posfeat_match_pairs; the tile plan
+ * (posfeat_match_pairs_splits), the output layout and the tie rule are that
+ * call's.  In addition: kp [N][2] fp32 keypoints (x, y), pool rows numbered as
+ * desc; model: 0 homography, 1 fundamental matrix; M [npairs][9] fp64
+ * row-major (device, 8-B aligned): what posfeat_ransac_homography /
+ * posfeat_ransac_fundamental write, used as given, never rescaled; thr in
+ * pixels, t2 = (float)(thr * thr).  Conventions of posfeat_ransac_fundamental:
+ * x1 = (x, y, 1) in image 1 (set s1), x2 = (u, v, 1) in image 2, x2^T F x1 =
+ * 0, x2 ~ H x1.  A descriptor of one image competes only against the keypoints
+ * of the other image the model admits: arg-max, second best and Lowe ratio are
+ * all taken over the admissible set.  No arithmetic below is contracted, each
+ * operation is rounded once.
+ *   records      one fp32 x 4 record per keypoint of the pair's two images,
+ *                built in fp64 by a prepass launch.  For a point (a, b) and a
+ *                matrix Q, q_k = (Q[k][0] a + Q[k][1] b) + Q[k][2], k = 0..2.
+ *                Fundamental: rec1[i] = (q0, q1, q2, q0 q0 + q1 q1) with Q = F
+ *                for image-1 point i, rec2[j] the same with Q = F^T for image-2
+ *                point j, each component rounded to fp32 last.  Homography:
+ *                rec1[i] = (q0 / q2, q1 / q2, 0, 0) with Q = H, rounded to fp32
+ *                last, no sign test on q2; rec2[j] = (u, v, 0, 0).
+ *   admissible   in fp32, inside the top-2 fold, from the streamed row's
+ *                record ra and the column's data.  Fundamental, side "rows of
+ *                sim" (streamed rows image 2, columns image 1): e = ((ra0 x) +
+ *                (ra1 y)) + ra2 with (x, y) the column's fp32 keypoint, den = ra3
+ *                + rec1[col].w; side "columns": the same with rec1 streamed, (u,
+ *                v) and rec2[col].w; both: admissible iff den > 0 and t2 den is
+ *                finite and e e <= t2 den.  Homography (either side): du = u -
+ *                px, dv = v - py with (px, py) from rec1 and (u, v) from rec2,
+ *                admissible iff (du du + dv dv) <= t2.  Any NaN fails.  A zero
+ *                model (status 1 from RANSAC) admits nothing: counts[p] = 0.
+ *                The two sides of a fundamental pair evaluate e from different
+ *                records and may disagree at the threshold; that is part of
+ *                the definition (a mutual match needs both).
+ *   fold         an inadmissible entry takes -inf, as a row past the range
+ *                does; the K = 128 chain, the k order and the strict '>' are
+ *                posfeat_match's.
+ *   select       posfeat_match's, plus: a row whose best value is -inf (no
+ *                admissible candidate) never matches, in any mode.  A row with a
+ *                single admissible candidate has second best -inf; its ratio is
+ *                d1 / (inf + 1e-8) = 0, which passes every ratio test.
+ * Returns, before any device work: posfeat_match_pairs's errors;
+ * POSFEAT_E_INVALID for a null kp or M, an M not 8-B aligned, a non-finite or
+ * non-positive thr; POSFEAT_E_UNSUPPORTED for a model outside 0..1;
+ * POSFEAT_E_WORKSPACE for ws_bytes below posfeat_match_pairs_guided_workspace
+ * (the unguided workspace plus a pair table and 16 B per keypoint per pair
+ * side; 0 for an invalid table).
+ * Launches: the record prepass, top-2, merge (only when a side is split),
+ * select.  Stream-ordered, never waits for its own kernels; NOT
+ * graph-capturable (the plan is copied from pageable host memory).
+ * Deterministic, and a pair's result does not depend on the rest of the list.
+ * posfeat_guided_record and posfeat_guided_admissible are host only (no
+ * device, no launch) and compile the text the kernels compile.
+ * posfeat_guided_record writes to rec[4] the record of the point pt[2] under
+ * M[9]: side 0 an image-1 point (rec1), side 1 an image-2 point (rec2).
+ * posfeat_guided_admissible returns 1 or 0 for a streamed record ra[4] and the
+ * column's data col[3]: fundamental (x, y, w) = the column's keypoint and the w
+ * of its record; homography (x, y, unused) = the column's record.  Both return
+ * POSFEAT_E_INVALID for a null pointer (a side outside 0..1, a non-finite or
+ * non-positive thr) and POSFEAT_E_UNSUPPORTED for a model outside 0..1. */
+size_t posfeat_match_pairs_guided_workspace(const int32_t *set_off, int nsets,
+                                            const int32_t *pairs, int npairs);
+int posfeat_guided_record(int model, int side, const double *M, const float *pt, float *rec);
+int posfeat_guided_admissible(int model, const float *ra, const float *col, double thr);
+int posfeat_match_pairs_guided(const float *desc, const float *kp, const int32_t *set_off,
+                               int nsets, const int32_t *pairs, int npairs, int dim, int mode,
+                               float ratio, int model, const double *M, double thr,
+                               int32_t *matches, int32_t *counts, void *ws, size_t ws_bytes,
+                               void *stream);
+
 /* The homography check of evaluations/hpatches/evaluation.py:69-90 on the
  * matches posfeat_match_pairs left: kp [N][2] fp32 keypoints (x, y) with the
  * row numbering of desc, set_off / pairs the same host tables, H [npairs][9]

@@ -217,6 +217,13 @@ SIGNATURES = {
     "posfeat_match_pairs": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                                     ctypes.c_float, c_void_p, c_void_p, c_void_p, c_size_t,
                                     c_void_p]),
+    "posfeat_match_pairs_guided_workspace": (c_size_t, [c_void_p, c_int, c_void_p, c_int]),
+    "posfeat_guided_record": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "posfeat_guided_admissible": (c_int, [c_int, c_void_p, c_void_p, ctypes.c_double]),
+    "posfeat_match_pairs_guided": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                           c_int, c_int, ctypes.c_float, c_int, c_void_p,
+                                           ctypes.c_double, c_void_p, c_void_p, c_void_p, c_size_t,
+                                           c_void_p]),
     "posfeat_reproj_hist_workspace": (c_size_t, [c_int]),
     "posfeat_reproj_hist": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                     c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),

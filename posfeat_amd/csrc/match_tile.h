@@ -7,6 +7,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "guided_solve.h"
 
 namespace pfmatch {
 
@@ -34,9 +35,25 @@ __device__ __forceinline__ Top2 top2_merge(const Top2& a, const Top2& b) {
 // As: 2 x MSTEP x MD floats of LDS, 16-B aligned.  The result is valid in the
 // lanes with (lane >> 5) == 0.  Each similarity is one K = 128 fmaf chain in a
 // fixed k order, so its bits do not depend on [r0, r1).
-__device__ __forceinline__ Top2 match_tile_top2(const float* __restrict__ A, int r0, int r1,
-                                                const float* __restrict__ B, int nb, int col,
-                                                float* As) {
+//
+// GUIDE (compile time): GUIDE_NONE is the plain tile.  GUIDE_H / GUIDE_F fold
+// only the rows guided_solve.h admits for this column under a homography / a
+// fundamental matrix (posfeat_match_pairs_guided): arec[i] is the record of A
+// row i, Rs 2 x MSTEP records of LDS beside As, (cx, cy, cw) the column's data
+// and t2 the squared threshold.  The records of a step travel with its
+// descriptors (one more 1 KB DMA by wave 0); the fold reads a row's record at
+// one address per lane half, a broadcast.  An inadmissible entry takes -inf,
+// as a row past r1 does; nothing before the fold differs.
+struct GuideCol {
+  float cx, cy, cw, t2;
+};
+constexpr int GUIDE_NONE = -1, GUIDE_H = pfguided::HOMOGRAPHY, GUIDE_F = pfguided::FUNDAMENTAL;
+
+template <int GUIDE>
+__device__ __forceinline__ Top2 match_tile_top2_g(const float* __restrict__ A, int r0, int r1,
+                                                  const float* __restrict__ B, int nb, int col,
+                                                  float* As, const f32x4* __restrict__ arec,
+                                                  float* Rs, const GuideCol& gc) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5;
   // this wave's B fragments: lane half h supplies k = 8g + 4h + j for MFMA j
   f32x4 breg[MD / 8];
@@ -61,6 +78,14 @@ __device__ __forceinline__ Top2 match_tile_top2(const float* __restrict__ A, int
           (__attribute__((address_space(3))) void*)(As + buf * MSTEP * MD +
                                                      (wave * (MSTEP / 8) + t) * 2 * MD),
           16, 0, 0);
+    }
+    if constexpr (GUIDE != GUIDE_NONE) {
+      if (wave == 0) {  // lane L: the record of row L of the step
+        const int row = min(r0 + s * MSTEP + lane, r1 - 1);
+        __builtin_amdgcn_global_load_lds(
+            (const __attribute__((address_space(1))) void*)(arec + row),
+            (__attribute__((address_space(3))) void*)(Rs + buf * MSTEP * 4), 16, 0, 0);
+      }
     }
   };
   Top2 best{-INFINITY, 0x7fffffff, -INFINITY};
@@ -100,7 +125,14 @@ __device__ __forceinline__ Top2 match_tile_top2(const float* __restrict__ A, int
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int i = ib + (r & 3) + 8 * (r >> 2);
-        const float v = i < r1 ? acc[r] : -INFINITY;
+        bool ok = i < r1;
+        if constexpr (GUIDE != GUIDE_NONE) {
+          const f32x4 ra = *reinterpret_cast<const f32x4*>(
+              Rs + (cur * MSTEP + mi * 32 + 4 * h + (r & 3) + 8 * (r >> 2)) * 4);
+          ok = ok && pfguided::admissible<GUIDE>(ra[0], ra[1], ra[2], ra[3], gc.cx, gc.cy, gc.cw,
+                                                 gc.t2);
+        }
+        const float v = ok ? acc[r] : -INFINITY;
         if (v > best.v1) {
           best.v2 = best.v1;
           best.v1 = v;
@@ -121,6 +153,13 @@ __device__ __forceinline__ Top2 match_tile_top2(const float* __restrict__ A, int
   return h == 0 ? top2_merge(best, o) : top2_merge(o, best);
 }
 
+__device__ __forceinline__ Top2 match_tile_top2(const float* __restrict__ A, int r0, int r1,
+                                                const float* __restrict__ B, int nb, int col,
+                                                float* As) {
+  return match_tile_top2_g<GUIDE_NONE>(A, r0, r1, B, nb, col, As, nullptr, nullptr,
+                                       GuideCol{0.f, 0.f, 0.f, 0.f});
+}
+
 // torch: sqrt(2 - 2 s) in fp32; ratio = d1 / (d2 + 1e-8)
 __device__ __forceinline__ float lowe_ratio(float s1, float s2) {
   const float d1 = __fsqrt_rn(__fsub_rn(2.f, __fmul_rn(2.f, s1)));
@@ -132,7 +171,10 @@ __device__ __forceinline__ float lowe_ratio(float s1, float s2) {
 // NN, 1 symmetric ratio, 2 mutual NN + symmetric ratio.  Each thread owns a
 // contiguous range of rows i, counts its matches, an exclusive scan in LDS
 // (off: 1024 ints) gives its output offset (matches come out in ascending i,
-// as the reference's boolean-mask indexing orders them).
+// as the reference's boolean-mask indexing orders them).  GUARD (the guided
+// call): a row whose best value is -inf had no admissible candidate and never
+// matches, in any mode (the clamp below would let mode 0 emit it).
+template <bool GUARD = false>
 __device__ __forceinline__ void match_select_pair(
     const int* __restrict__ nn12, const float* __restrict__ r1a, const float* __restrict__ r1b,
     const int* __restrict__ nn21, const float* __restrict__ r2a, const float* __restrict__ r2b,
@@ -141,6 +183,9 @@ __device__ __forceinline__ void match_select_pair(
   const int t = threadIdx.x, per = (n1 + 1023) / 1024;
   const int i0 = min(n1, t * per), i1 = min(n1, i0 + per);
   auto keep = [&](int i) {
+    if constexpr (GUARD) {
+      if (r1a[i] == -INFINITY) return false;
+    }
     // a row of NaN similarities keeps the fold's initial index: stay in bounds
     const int j = min(nn12[i], n2 - 1);
     bool k = true;

@@ -25,6 +25,13 @@
 // The A-row split is chosen for the whole grid (match_plan.h), not per pair:
 // with hundreds of pairs no side is split.
 //
+// posfeat_match_pairs_guided is the same plan and the same launches with the
+// candidates of each pair restricted by its 3x3 model (guided_solve.h):
+// gd_record_kernel builds one fp32x4 record per keypoint per pair side in
+// fp64, gd_top2_kernel<GUIDE> is mp_top2_kernel on match_tile_top2_g<GUIDE>
+// (the step's records beside its descriptors in LDS, the fp32 predicate in the
+// fold), mp_merge_kernel as is, gd_select_kernel = match_select_pair<true>.
+//
 // posfeat_reproj_hist: one workgroup per pair; per match the fp64 projection
 // and distance of evaluation.py:71-78, binned by ceil(dist) with LDS integer
 // atomics and prefix-summed into the cumulative counts of lines 86-90.
@@ -131,6 +138,117 @@ __global__ __launch_bounds__(1024) void mp_select_kernel(const Side* __restrict_
                     matches + 2 * (long long)r.moff, counts + p, off);
 }
 
+// ---- guided matching (posfeat_match_pairs_guided) ---------------------------
+// The records of pair p lie at rec_off entries of the record plane: rec1[n1]
+// (image 1 = set s1) then rec2[n2]; a pair with an empty side has none.
+struct GuidePair {  // 32 bytes
+  int64_t rec_off;
+  int32_t off1, n1, off2, n2, pad[2];
+};
+static_assert(sizeof(GuidePair) == 32, "device table layout");
+
+// one thread per record: find its pair, build it in fp64 (guided_solve.h)
+__global__ void gd_record_kernel(const float* __restrict__ kp, const double* __restrict__ M,
+                                 const GuidePair* __restrict__ gp, int npairs, long long total,
+                                 int model, f32x4* __restrict__ rec) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  int lo = 0, hi = npairs - 1;  // the last pair with rec_off <= e (empty pairs precede it)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (gp[mid].rec_off <= e) lo = mid; else hi = mid - 1;
+  }
+  const GuidePair g = gp[lo];
+  const int k = (int)(e - g.rec_off);
+  if (k >= g.n1 + g.n2) return;
+  const int side = k < g.n1 ? 0 : 1;
+  const float* pt = kp + 2 * ((long long)(side ? g.off2 : g.off1) + (side ? k - g.n1 : k));
+  double m[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) m[i] = M[(long long)lo * 9 + i];
+  float r[4];
+  pfguided::record(model, side, m, pt[0], pt[1], r);
+  rec[e] = f32x4{r[0], r[1], r[2], r[3]};
+}
+
+template <int GUIDE>
+__global__ __launch_bounds__(256) void gd_top2_kernel(
+    const float* __restrict__ desc, const float* __restrict__ kp, const Side* __restrict__ sides,
+    const Tile* __restrict__ tiles, const GuidePair* __restrict__ gp,
+    const f32x4* __restrict__ rec, float t2, char* __restrict__ merged, char* __restrict__ parts) {
+  __shared__ __attribute__((aligned(16))) float As[2 * MSTEP * MD];  // 2 x 32 KB
+  __shared__ __attribute__((aligned(16))) float Rs[2 * MSTEP * 4];   // 2 x 1 KB
+  const Tile t = tiles[blockIdx.x];
+  const Side s = sides[t.side];
+  const GuidePair g = gp[t.side >> 1];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int col = t.cb * MCOLS + wave * 32 + (lane & 31);
+  const int r0 = t.split * s.rps;
+  const int r1 = s.na - r0 > s.rps ? r0 + s.rps : s.na;
+  // side 2p streams image 2 against the columns of image 1, side 2p + 1 the reverse
+  const bool rows = (t.side & 1) == 0;
+  const f32x4* arec = rec + g.rec_off + (rows ? g.n1 : 0);
+  const f32x4* brec = rec + g.rec_off + (rows ? 0 : g.n1);
+  const int cc = min(col, s.nb - 1);
+  const f32x4 rc = brec[cc];
+  GuideCol gc;
+  if constexpr (GUIDE == GUIDE_F) {
+    const float* pt = kp + 2 * ((long long)s.b_off + cc);
+    gc = GuideCol{pt[0], pt[1], rc[3], t2};
+  } else {
+    gc = GuideCol{rc[0], rc[1], 0.f, t2};
+  }
+  const Top2 best = match_tile_top2_g<GUIDE>(desc + (long long)s.a_off * MD, r0, r1,
+                                             desc + (long long)s.b_off * MD, s.nb, col, As, arec,
+                                             Rs, gc);
+  if ((lane >> 5) == 0 && col < s.nb) {
+    if (s.nsplit == 1) {
+      const SideOut o = side_out(merged, s);
+      o.nn[col] = best.i1;
+      o.v1[col] = best.v1;
+      o.v2[col] = best.v2;
+    } else {
+      char* b = parts + s.part_off * 12;
+      const size_t plane = (size_t)s.nsplit * s.nb * 4;
+      const size_t p = (size_t)t.split * s.nb + col;
+      reinterpret_cast<float*>(b)[p] = best.v1;
+      reinterpret_cast<int*>(b + plane)[p] = best.i1;
+      reinterpret_cast<float*>(b + 2 * plane)[p] = best.v2;
+    }
+  }
+}
+
+__global__ __launch_bounds__(1024) void gd_select_kernel(const Side* __restrict__ sides,
+                                                         char* __restrict__ merged, int mode,
+                                                         float ratio, int* __restrict__ matches,
+                                                         int* __restrict__ counts) {
+  __shared__ int off[1024];
+  const int p = blockIdx.x;
+  const Side r = sides[2 * p], c = sides[2 * p + 1];
+  if (r.nb <= 0 || c.nb <= 0) {
+    if (threadIdx.x == 0) counts[p] = 0;
+    return;
+  }
+  const SideOut ro = side_out(merged, r), co = side_out(merged, c);
+  match_select_pair<true>(ro.nn, ro.v1, ro.v2, co.nn, co.v1, co.v2, r.nb, c.nb, mode, ratio,
+                          matches + 2 * (long long)r.moff, counts + p, off);
+}
+
+// the guided call's workspace: the plan's, then the GuidePair table, then the records
+struct GuideLayout {
+  size_t gp_off, rec_off, total_bytes;
+  long long nrec;
+};
+GuideLayout guide_layout(const Plan& pl, int npairs) {
+  GuideLayout L;
+  L.nrec = 0;
+  for (int p = 0; p < npairs; ++p) L.nrec += (long long)pl.sides[2 * (size_t)p].nb + pl.sides[2 * (size_t)p].na;
+  L.gp_off = pf_align(pl.total_bytes, 256);
+  L.rec_off = L.gp_off + pf_align((size_t)npairs * sizeof(GuidePair), 256);
+  L.total_bytes = L.rec_off + pf_align((size_t)L.nrec * 16, 256) + 256;
+  return L;
+}
+
 struct ReprojPair {  // 32 bytes
   int32_t a_off, n1, b_off, n2, moff, pad[3];
 };
@@ -231,6 +349,111 @@ extern "C" int posfeat_match_pairs(const float* desc, const int32_t* set_off, in
     PF_CHECK_LAUNCH();
   }
   hipLaunchKernelGGL(mp_select_kernel, dim3(npairs), dim3(1024), 0, st, sides, merged, mode, ratio,
+                     matches, counts);
+  PF_CHECK_LAUNCH();
+  return POSFEAT_OK;
+}
+
+extern "C" size_t posfeat_match_pairs_guided_workspace(const int32_t* set_off, int nsets,
+                                                       const int32_t* pairs, int npairs) {
+  Plan pl;
+  if (pfmatch_plan::build_plan(set_off, nsets, pairs, npairs, false, pl) != 0) return 0;
+  return guide_layout(pl, npairs).total_bytes;
+}
+
+extern "C" int posfeat_guided_record(int model, int side, const double* M, const float* pt,
+                                     float* rec) {
+  if (!M || !pt || !rec || side < 0 || side > 1) return POSFEAT_E_INVALID;
+  if (model < 0 || model > 1) return POSFEAT_E_UNSUPPORTED;
+  float r[4];
+  pfguided::record(model, side, M, pt[0], pt[1], r);
+  for (int i = 0; i < 4; ++i) rec[i] = r[i];
+  return POSFEAT_OK;
+}
+
+extern "C" int posfeat_guided_admissible(int model, const float* ra, const float* col,
+                                         double thr) {
+  if (!ra || !col || !(thr > 0.0) || !(thr < (double)INFINITY)) return POSFEAT_E_INVALID;
+  if (model < 0 || model > 1) return POSFEAT_E_UNSUPPORTED;
+  const float t2 = (float)(thr * thr);
+  return model == pfguided::FUNDAMENTAL
+             ? pfguided::admissible<pfguided::FUNDAMENTAL>(ra[0], ra[1], ra[2], ra[3], col[0],
+                                                           col[1], col[2], t2)
+             : pfguided::admissible<pfguided::HOMOGRAPHY>(ra[0], ra[1], ra[2], ra[3], col[0],
+                                                          col[1], col[2], t2);
+}
+
+extern "C" int posfeat_match_pairs_guided(const float* desc, const float* kp,
+                                          const int32_t* set_off, int nsets, const int32_t* pairs,
+                                          int npairs, int dim, int mode, float ratio, int model,
+                                          const double* M, double thr, int32_t* matches,
+                                          int32_t* counts, void* ws, size_t ws_bytes,
+                                          void* stream) {
+  if (!desc || !kp || !M || !set_off || !pairs || !matches || !counts || !ws || nsets <= 0 ||
+      npairs <= 0)
+    return POSFEAT_E_INVALID;
+  if (dim != MD || mode < 0 || mode > 2 || model < 0 || model > 1) return POSFEAT_E_UNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(desc) & 15) || (reinterpret_cast<uintptr_t>(ws) & 255) ||
+      (reinterpret_cast<uintptr_t>(M) & 7))
+    return POSFEAT_E_INVALID;
+  if (!(thr > 0.0) || !(thr < (double)INFINITY)) return POSFEAT_E_INVALID;
+  Plan pl;
+  if (pfmatch_plan::build_plan(set_off, nsets, pairs, npairs, true, pl) != 0)
+    return POSFEAT_E_INVALID;
+  const GuideLayout L = guide_layout(pl, npairs);
+  if (ws_bytes < L.total_bytes) return POSFEAT_E_WORKSPACE;
+  std::vector<GuidePair> gtab((size_t)npairs);
+  long long nrec = 0;
+  for (int p = 0; p < npairs; ++p) {
+    const Side& r = pl.sides[2 * (size_t)p];  // B = set s1, A = set s2
+    gtab[p] = GuidePair{nrec, r.b_off, r.nb, r.a_off, r.na, {0, 0}};
+    nrec += (long long)r.nb + r.na;
+  }
+  hipStream_t st = pf_stream(stream);
+  char* w = static_cast<char*>(ws);
+  // pageable sources, read by the runtime before the copy calls return (as in
+  // posfeat_match_pairs), so the tables may die with us
+  if (hipMemcpyAsync(w, pl.sides.data(), pl.sides.size() * sizeof(Side), hipMemcpyHostToDevice,
+                     st) != hipSuccess)
+    return POSFEAT_E_HIP;
+  if (pl.ntiles > 0 &&
+      hipMemcpyAsync(w + pl.tiles_off, pl.tiles.data(), pl.tiles.size() * sizeof(Tile),
+                     hipMemcpyHostToDevice, st) != hipSuccess)
+    return POSFEAT_E_HIP;
+  if (hipMemcpyAsync(w + L.gp_off, gtab.data(), gtab.size() * sizeof(GuidePair),
+                     hipMemcpyHostToDevice, st) != hipSuccess)
+    return POSFEAT_E_HIP;
+  const Side* sides = reinterpret_cast<const Side*>(w);
+  const Tile* tiles = reinterpret_cast<const Tile*>(w + pl.tiles_off);
+  const GuidePair* gp = reinterpret_cast<const GuidePair*>(w + L.gp_off);
+  f32x4* rec = reinterpret_cast<f32x4*>(w + L.rec_off);
+  char* merged = w + pl.merged_off;
+  char* parts = w + pl.part_off;
+  const float t2 = (float)(thr * thr);
+  if (nrec > 0) {
+    const long long blocks = (nrec + 255) / 256;
+    if (blocks > INT32_MAX) return POSFEAT_E_INVALID;
+    hipLaunchKernelGGL(gd_record_kernel, dim3((unsigned)blocks), dim3(256), 0, st, kp, M, gp,
+                       npairs, nrec, model, rec);
+    PF_CHECK_LAUNCH();
+  }
+  if (pl.ntiles > 0) {
+    if (model == pfguided::FUNDAMENTAL)
+      hipLaunchKernelGGL(gd_top2_kernel<GUIDE_F>, dim3((unsigned)pl.ntiles), dim3(256), 0, st, desc,
+                         kp, sides, tiles, gp, rec, t2, merged, parts);
+    else
+      hipLaunchKernelGGL(gd_top2_kernel<GUIDE_H>, dim3((unsigned)pl.ntiles), dim3(256), 0, st, desc,
+                         kp, sides, tiles, gp, rec, t2, merged, parts);
+    PF_CHECK_LAUNCH();
+  }
+  if (pl.part_entries > 0) {
+    const long long blocks = (pl.merged_entries + 255) / 256;
+    if (blocks > INT32_MAX) return POSFEAT_E_INVALID;
+    hipLaunchKernelGGL(mp_merge_kernel, dim3((unsigned)blocks), dim3(256), 0, st, sides,
+                       (int)pl.sides.size(), (long long)pl.merged_entries, merged, parts);
+    PF_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(gd_select_kernel, dim3(npairs), dim3(1024), 0, st, sides, merged, mode, ratio,
                      matches, counts);
   PF_CHECK_LAUNCH();
   return POSFEAT_OK;

@@ -5,7 +5,7 @@ match_features and geometric_verification), without the COLMAP database.
 
   verify_pair_list(feature_dir, pairs_file, postfix, matcher="mnn", ratio=0.95,
                    model="fundamental", chunk=1024, iters=2048, thr=4.0, seed=0,
-                   output=None, intrinsics=None) -> dict
+                   output=None, intrinsics=None, guided=False) -> dict
 
 ``pairs_file`` holds one ``name1 name2`` per line (image_pairs_to_match.txt);
 the features of image ``name`` are ``feature_dir/name.postfix`` as extract.py
@@ -31,6 +31,16 @@ The returned dict, also written to ``output`` (np.savez) when given:
 and for ``model="essential"`` only:
   pose           [npairs, 3, 4] fp64 [R | t], x2 ~ R x1 + t, |t| = 1
   cheir          [npairs, 2] int32 (decomposition index, matches in front)
+
+``guided=True`` (COLMAP's guided matching): after RANSAC the chunk's pairs are
+matched again by geometry.guided_pairs under the model just found, with the
+same ``thr``, matcher and ratio, every descriptor competing only against the
+keypoints the model admits (the essential model guides with F = K2^-T E K1^-1
+and needs cameras without distortion, k1 = 0).  ``matches`` / ``match_offsets``
+then hold the guided matches, and
+  n_verified     [npairs] int32 the RANSAC inlier counts they replace
+is added; still one copy and one synchronisation per chunk.  Without the flag
+the output is what it always was.
 """
 import os
 
@@ -65,10 +75,30 @@ def _read_feats(feature_dir, name, postfix):
             np.ascontiguousarray(aux["descriptors"], dtype=np.float32))
 
 
+def _guide_model(model, cams, images, pairs, device):
+    """the 3x3 model the guided call takes: F or H as RANSAC left it; for an
+    essential matrix F = K2^-T E K1^-1 (torch ops on the device, from the
+    inverse calibration matrices built here on the host)"""
+    if cams is None:
+        return model
+    kinv = np.zeros((len(images), 3, 3))
+    for i, n in enumerate(images):
+        fx, fy, cx, cy, k1 = (float(v) for v in cams[n][:5])
+        if k1 != 0.0:
+            raise ValueError("guided matching under an essential matrix needs cameras without "
+                             "distortion (k1 = %g for %s)" % (k1, n))
+        kinv[i] = [[1 / fx, 0, -cx / fx], [0, 1 / fy, -cy / fy], [0, 0, 1]]
+    kinv = torch.from_numpy(kinv).to(device)
+    k1i = kinv[torch.from_numpy(pairs[:, 0].astype(np.int64)).to(device)]
+    k2i = kinv[torch.from_numpy(pairs[:, 1].astype(np.int64)).to(device)]
+    return torch.matmul(k2i.transpose(1, 2), torch.matmul(model, k1i)).contiguous()
+
+
 def _run_chunk(feature_dir, postfix, names, device, matcher, ratio, fit, iters, thr, seed,
-               cams=None):
+               cams=None, guided=False):
     """names: [(name1, name2)] -> host (counts, matches [sum n1, 2], moff, model, info, mask),
-    and with ``cams`` ({image name: camera row}, the essential model) pose and cheir"""
+    and with ``cams`` ({image name: camera row}, the essential model) pose and cheir; with
+    ``guided`` the guided call's (counts, matches) come last"""
     images = sorted({n for pair in names for n in pair})
     index = {n: i for i, n in enumerate(images)}
     feats = [_read_feats(feature_dir, n, postfix) for n in images]
@@ -86,6 +116,12 @@ def _run_chunk(feature_dir, postfix, names, device, matcher, ratio, fit, iters, 
         rows = torch.from_numpy(np.stack([cams[n] for n in images]).astype(np.float64)).to(device)
         model, pose, info, cheir, inlier = fit(kp_pool, rows, batch, iters=iters, thr=thr, seed=seed)
         extra = [pose.view(torch.uint8).view(-1), cheir.view(torch.uint8).view(-1)]
+    if guided:
+        gbatch = geometry.guided_pairs(
+            kp_pool, batch, "homography" if fit is geometry.ransac_homography_pairs
+            else "fundamental", _guide_model(model, cams, images, pairs, device), thr, matcher,
+            ratio)
+        extra = extra + [gbatch.buf.view(torch.uint8)]
     # one synchronisation: everything into one pinned byte buffer
     parts = [batch.buf.view(torch.uint8), model.view(torch.uint8).view(-1),
              info.view(torch.uint8).view(-1), inlier] + extra
@@ -106,12 +142,15 @@ def _run_chunk(feature_dir, postfix, names, device, matcher, ratio, fit, iters, 
     if cams is not None:
         out += (h[cuts[4]:cuts[5]].copy().view(np.float64).reshape(npairs, 3, 4),
                 h[cuts[5]:cuts[6]].copy().view(np.int32).reshape(npairs, 2))
+    if guided:
+        gbuf = h[cuts[-2]:cuts[-1]].copy().view(np.int32)
+        out += (gbuf[:npairs], gbuf[npairs:].reshape(-1, 2))
     return out
 
 
 def verify_pair_list(feature_dir, pairs_file, postfix, matcher="mnn", ratio=0.95,
                      model="fundamental", chunk=1024, iters=None, thr=None, seed=0, output=None,
-                     intrinsics=None):
+                     intrinsics=None, guided=False):
     if model not in MODELS:
         raise ValueError("model must be one of %s" % sorted(MODELS))
     if (model == "essential") != (intrinsics is not None):
@@ -135,17 +174,22 @@ def verify_pair_list(feature_dir, pairs_file, postfix, matcher="mnn", ratio=0.95
         if missing:
             raise ValueError("no intrinsics for %s" % ", ".join(missing[:5]))
     kept, offsets, models, infos, raw, poses, cheirs = [], [0], [], [], [], [], []
+    guided = bool(guided)
     for at in range(0, len(names), int(chunk)):
         part = names[at:at + int(chunk)]
         got = _run_chunk(feature_dir, postfix, part, device, matcher, ratio, fit, iters, thr, seed,
-                         cams)
+                         cams, guided)
         counts, matches, moff, M, info, mask = got[:6]
         if cams is not None:
             poses.append(got[6])
             cheirs.append(got[7])
         for p in range(len(part)):
-            rows = slice(int(moff[p]), int(moff[p]) + int(counts[p]))
-            kept.append(matches[rows][mask[rows]])
+            if guided:
+                gcounts, gmatches = got[-2:]
+                kept.append(gmatches[int(moff[p]):int(moff[p]) + int(gcounts[p])])
+            else:
+                rows = slice(int(moff[p]), int(moff[p]) + int(counts[p]))
+                kept.append(matches[rows][mask[rows]])
             offsets.append(offsets[-1] + kept[-1].shape[0])
         models.append(M)
         infos.append(info)
@@ -161,6 +205,8 @@ def verify_pair_list(feature_dir, pairs_file, postfix, matcher="mnn", ratio=0.95
     if cams is not None:
         out.update(pose=np.concatenate(poses, 0) if poses else np.zeros((0, 3, 4)),
                    cheir=np.concatenate(cheirs, 0) if cheirs else np.zeros((0, 2), np.int32))
+    if guided:
+        out.update(n_verified=out["info"][:, 1].astype(np.int32))
     if output is not None:
         with open(output, "wb") as f:
             np.savez(f, **out)

@@ -20,6 +20,11 @@ score, selection, refit) are in include/posfeat_hip.h; no CPU path.
         distance in pixels and info[p, 3] = refit_kept | root << 8.
   find_fundamental(kp1, kp2, matches, iters=2048, thr=4.0, seed=0)
         one pair, numpy in and out: (F [3, 3], mask [m] bool, info [4]).
+  guided_pairs(kp_pool, batch, model, M, thr, matcher="mnn", ratio=0.95)
+        -> PairBatch: posfeat_match_pairs_guided (matchpairs.hip) on the tables
+        of ``batch``: the matchers again, each descriptor competing only against
+        the keypoints the pair's verified H or F admits within thr pixels.
+        guided_record / guided_admissible are its host-only record and predicate.
   ransac_essential_pairs(kp_pool, cams, batch, iters=1024, thr=4.0, seed=0)
         -> (E [npairs, 3, 3] fp64, pose [npairs, 3, 4] fp64, info [npairs, 4],
         cheir [npairs, 2] int32, inlier): posfeat_ransac_essential
@@ -189,6 +194,45 @@ def ransac_fundamental_pairs(kp_pool, batch, iters=2048, thr=4.0, seed=0):
     the arguments of ransac_homography_pairs.  thr = 4 px is COLMAP's two-view
     max_error default."""
     return _ransac_pairs("fundamental", kp_pool, batch, iters, thr, seed)
+
+
+def guided_pairs(kp_pool, batch, model, M, thr, matcher="mnn", ratio=0.95):
+    """posfeat_match_pairs_guided on the tables of an existing PairBatch: the
+    pairs of ``batch`` matched again with the candidates restricted to those
+    the verified model M[p] ("homography" or "fundamental", [npairs, 3, 3] fp64
+    on the device, as ransac_*_pairs return it) admits within ``thr`` pixels.
+    Returns a new PairBatch with the layout of ``batch``."""
+    return matchers.match_pairs_guided_device(batch.pool, kp_pool, batch.set_off, batch.pairs,
+                                              model, M, thr, matcher, ratio)
+
+
+def guided_record(model, side, M, pt):
+    """posfeat_guided_record (host only, needs no device): the fp32 x 4 record
+    of the point ``pt`` (x, y) under M [3, 3]; side 0 an image-1 point, side 1
+    an image-2 point; model 0 homography, 1 fundamental matrix."""
+    M = np.ascontiguousarray(M, dtype=np.float64).reshape(9)
+    pt = np.ascontiguousarray(pt, dtype=np.float32).reshape(2)
+    out = np.zeros(4, dtype=np.float32)
+    r = lib().posfeat_guided_record(int(model), int(side), ctypes.c_void_p(M.ctypes.data),
+                                    ctypes.c_void_p(pt.ctypes.data),
+                                    ctypes.c_void_p(out.ctypes.data))
+    if r != 0:
+        raise ValueError("posfeat_guided_record failed (%d)" % r)
+    return out
+
+
+def guided_admissible(model, ra, col, thr):
+    """posfeat_guided_admissible (host only, needs no device): the fp32
+    predicate of the guided fold for a streamed record ra [4] and the column's
+    data col [3] (fundamental: its keypoint and the w of its record;
+    homography: its record's x, y)."""
+    ra = np.ascontiguousarray(ra, dtype=np.float32).reshape(4)
+    col = np.ascontiguousarray(col, dtype=np.float32).reshape(3)
+    r = lib().posfeat_guided_admissible(int(model), ctypes.c_void_p(ra.ctypes.data),
+                                        ctypes.c_void_p(col.ctypes.data), float(thr))
+    if r < 0:
+        raise ValueError("posfeat_guided_admissible failed (%d)" % r)
+    return bool(r)
 
 
 def ransac_essential_pairs(kp_pool, cams, batch, iters=1024, thr=4.0, seed=0):

@@ -20,6 +20,11 @@ the current device.  No CPU path.
   match_pairs(descs, pairs, matcher="mnn", ratio=0.95)   the same matchers over a
         pair list (matchpairs.hip): four launches and one host read for the
         whole list, results bit-identical to the per-pair functions
+  match_pairs_guided_device(pool, kp_pool, set_off, pairs, model, M, thr,
+                            matcher="mnn", ratio=0.95)
+        the pair-list matchers with the candidates of each pair restricted to
+        those its verified homography or fundamental matrix admits within thr
+        pixels (posfeat_match_pairs_guided); device tensors in, a PairBatch out
 """
 import ctypes
 
@@ -151,6 +156,55 @@ def match_pairs_device(pool, set_off, pairs, matcher="mnn", ratio=0.95):
                                     int(pool.shape[1]), _MODES[matcher], float(ratio),
                                     ptr(batch.matches), ptr(batch.counts), ptr(ws), need,
                                     stream_ptr(pool.device)))
+    return batch
+
+
+_MODELS = {"homography": 0, "fundamental": 1, 0: 0, 1: 1}
+
+
+def match_pairs_guided_device(pool, kp_pool, set_off, pairs, model, M, thr, matcher="mnn",
+                              ratio=0.95):
+    """posfeat_match_pairs_guided: match_pairs_device with the candidates of pair
+    p restricted to those its model M[p] admits within ``thr`` pixels.  kp_pool:
+    [N, 2] fp32 device tensor numbered as ``pool``; model: "homography" / 0 or
+    "fundamental" / 1; M: [npairs, 3, 3] fp64 device tensor, what
+    geometry.ransac_homography_pairs / ransac_fundamental_pairs return (a zero
+    model admits nothing).  Returns a PairBatch laid out as match_pairs_device's,
+    nothing read back (stream-ordered)."""
+    _lib.require_device(pool)
+    if matcher not in _MODES:
+        raise ValueError("matcher must be one of %s" % sorted(_MODES))
+    if model not in _MODELS:
+        raise ValueError("model must be 'homography' (0) or 'fundamental' (1)")
+    set_off = np.ascontiguousarray(set_off, dtype=np.int32)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    npairs, nsets = pairs.shape[0], set_off.shape[0] - 1
+    if pairs.size and (pairs.min() < 0 or pairs.max() >= nsets):
+        raise IndexError("pair index out of range for %d descriptor sets" % nsets)
+    if (not torch.is_tensor(kp_pool) or kp_pool.dtype != torch.float32 or kp_pool.dim() != 2 or
+            kp_pool.shape[1] != 2 or kp_pool.device != pool.device):
+        raise ValueError("kp_pool must be a [N, 2] float32 tensor on the pool's device")
+    if kp_pool.shape[0] < int(set_off[-1]) or pool.shape[0] < int(set_off[-1]):
+        raise ValueError("the pools have fewer rows than the sets")
+    if (not torch.is_tensor(M) or M.dtype != torch.float64 or M.numel() != 9 * npairs or
+            M.device != pool.device):
+        raise ValueError("M must be a [npairs, 3, 3] float64 tensor on the pool's device")
+    if not (np.isfinite(thr) and thr > 0):
+        raise ValueError("thr must be a positive number of pixels")
+    kp_pool, M = kp_pool.contiguous(), M.contiguous()
+    n1 = (set_off[1:] - set_off[:-1])[pairs[:, 0]].astype(np.int64)
+    moff = np.concatenate([[0], np.cumsum(n1)])
+    need = lib().posfeat_match_pairs_guided_workspace(_host_ptr(set_off), nsets, _host_ptr(pairs),
+                                                      npairs)
+    if need == 0:
+        raise ValueError("invalid set offsets, or more than 2^31 - 1 match rows in one call")
+    ws = torch.empty(need, dtype=torch.uint8, device=pool.device)
+    buf = torch.empty(npairs + 2 * int(moff[-1]), dtype=torch.int32, device=pool.device)
+    batch = PairBatch(pool, set_off, pairs, moff, buf)
+    check(lib().posfeat_match_pairs_guided(
+        ptr(pool), ptr(kp_pool), _host_ptr(set_off), nsets, _host_ptr(pairs), npairs,
+        int(pool.shape[1]), _MODES[matcher], float(ratio), _MODELS[model], ptr(M), float(thr),
+        ptr(batch.matches), ptr(batch.counts), ptr(ws), need, stream_ptr(pool.device)))
     return batch
 
 

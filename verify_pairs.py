@@ -3,7 +3,11 @@ match_features + geometric_verification of evaluations/aachen/reconstruct_pipeli
 on the GPU and without the COLMAP database):
 ``python verify_pairs.py --features DIR --pairs image_pairs_to_match.txt --postfix NAME
 --out verified.npz [--matcher mnn|ratio|mnn_ratio] [--ratio R] [--model fundamental|homography]
-[--ransac_iters N] [--ransac_thr T] [--seed S] [--chunk PAIRS]``.
+[--ransac_iters N] [--ransac_thr T] [--seed S] [--chunk PAIRS] [--guided]``.
+``--guided`` matches every pair again under the model RANSAC found, each
+descriptor competing only against the keypoints that model admits within the
+RANSAC threshold (COLMAP's guided matching): ``matches`` then holds the guided
+matches and the .npz gains ``n_verified``, the inlier counts they replace.
 ``--model essential --intrinsics database_intrinsics.txt`` fits five-point
 essential matrices and relative poses between the calibrated cameras instead
 (the .npz gains ``pose`` and ``cheir``); with ``--nvm MODEL.nvm`` it also prints
@@ -34,21 +38,28 @@ if __name__ == "__main__":
     parser.add_argument("--chunk", type=int, default=1024)
     parser.add_argument("--intrinsics", type=str, default=None)
     parser.add_argument("--nvm", type=str, default=None)
+    parser.add_argument("--guided", action="store_true")
     args = parser.parse_args()
     if args.model == "essential" and args.intrinsics is None:
         parser.error("--model essential requires --intrinsics FILE")
     if args.nvm is not None and args.model != "essential":
         parser.error("--nvm goes with --model essential")
     extra = {} if args.intrinsics is None else {"intrinsics": args.intrinsics}
+    if args.guided:
+        extra["guided"] = True
     res = verification.verify_pair_list(
         args.features, args.pairs, args.postfix, matcher=args.matcher, ratio=args.ratio,
         model=args.model, chunk=args.chunk, iters=args.ransac_iters, thr=args.ransac_thr,
         seed=args.seed, output=args.out, **extra)
     info = res["info"]
     n = info.shape[0]
+    verified = int(res["n_verified"].sum()) if args.guided else int(res["matches"].shape[0])
     print("# Pairs: {:d}, with a model: {:d}; matches {:d}, verified {:d} ({:.3f})".format(
-        n, int(np.sum(info[:, 0] == 0)), int(res["n_matches"].sum()), int(res["matches"].shape[0]),
-        res["matches"].shape[0] / max(1, int(res["n_matches"].sum()))))
+        n, int(np.sum(info[:, 0] == 0)), int(res["n_matches"].sum()), verified,
+        verified / max(1, int(res["n_matches"].sum()))))
+    if args.guided:
+        print("# Guided matches: {:d} ({:.3f} of the verified)".format(
+            int(res["matches"].shape[0]), res["matches"].shape[0] / max(1, verified)))
     if args.nvm is not None:
         from posfeat_amd.evaluation import reconstruction, relative_pose
         gt = {n: np.concatenate([reconstruction.quat_to_rot(q), t[:, None]], 1)
