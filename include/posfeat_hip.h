@@ -1287,6 +1287,114 @@ int posfeat_refine_points(const float *kp, const int32_t *set_off, int nsets, co
 int posfeat_refine_point(const double *obs, int n, const double *X0, int steps, double *X,
                          double *cost);
 
+/* Split tracks: sequential RANSAC over the members a track's RANSAC left out.
+ * posfeat_triangulate makes one point per connected component of the match
+ * graph and drops every member that is not an inlier of it; in `colmap
+ * point_triangulator`, the step that call stands in for, an observation that
+ * did not join a point stays free and is triangulated again with its own
+ * correspondences.  One wrong verified match that ties two real tracks together
+ * costs the smaller one there; this call gets it back.  Opt-in: it takes a
+ * posfeat_triangulate result and returns a result of the same shape in which a
+ * track may have become several.  All in fp64.
+ * set_off is a HOST table; every other pointer is a device pointer.
+ *   kp, set_off, nsets, cams, poses   as posfeat_triangulate takes them, N =
+ *                set_off[nsets] pool rows
+ *   points_in [tmax][3], err_in [tmax], tinfo_in [tmax][4], track_off_in [tmax
+ *   + 1], track_rows_in [mmax], inlier_in [mmax], counts_in [8]   what a
+ *                posfeat_triangulate call left (its points, err, tinfo,
+ *                track_off, track_rows, obs_inlier, counts); T = counts_in[0]
+ *                clamped to [0, tmax] is read on the device.  None of them is
+ *                written.  tmax, mmax are the capacities of the buffers
+ *                (posfeat_triangulate's Tmax, Mmax).  A flag is set when its
+ *                byte is not 0;
+ *   iters, thr, min_angle_deg, seed   posfeat_triangulate's, with its ranges;
+ *   rounds       1..4: the generations a track runs at the most;
+ *   tmax_out     >= tmax: the track capacity of the output;
+ *   parents      an input track ("parent") t has the m members track_rows_in[
+ *                track_off_in[t] ..], numbered 0 .. m - 1 in that order, which
+ *                is ascending row order in a posfeat_triangulate result.  Its
+ *                left-over list L_1 is its unflagged members in member order.
+ *                A parent is carried through unchanged when its status is not
+ *                0, when |L_1| < 2, or when its member range is not inside [0,
+ *                mmax] or has more than 1024 members (posfeat_refine_points'
+ *                rule: nothing is read or written through such a range, so the
+ *                range of the output track_rows and obs_inlier is not written
+ *                either);
+ *   generations  generation g = 1 .. rounds takes L_g while |L_g| >= 2 and runs
+ *                exactly posfeat_triangulate's `hypotheses`, `score`,
+ *                `selection` and `refit` on L_g as if L_g were a track: the
+ *                members of L_g in order, rho = L_g[0], the same seed and the
+ *                same rule for iters (the same device functions).  A member
+ *                whose row is outside [0, N) is never an inlier and nothing is
+ *                read through it: a hypothesis whose pair holds one is
+ *                rejected.  If every hypothesis is rejected, or fewer than 2
+ *                members are inliers of the final point, the parent stops.
+ *                Otherwise child g exists: that point, err as
+ *                posfeat_triangulate defines it, tinfo {0, n_inliers, best_h,
+ *                refit_kept}, and its members are those final inliers.  L_g+1 =
+ *                L_g without them, in order;
+ *   numbering    parent t with c_t children becomes 1 + c_t output tracks, in
+ *                this order: the parent, child 1 .. c_t; the output tracks are
+ *                numbered in parent order by a scan on the device.  Under the
+ *                capacity: walking the tracks in output order, a child is
+ *                created iff its number plus the number of parents after its
+ *                own stays below tmax_out, so every parent has a place
+ *                whatever the children before it; the children that are not
+ *                created are then the last ones in output order.  The rows of
+ *                a child that is not created stay with the parent;
+ *   partition    the members of a parent and of its created children together
+ *                occupy the parent's range of track_rows_in, parent first; each
+ *                output track lists its members in member order.  A child's
+ *                members are its inliers, all flagged 1.  The parent keeps
+ *                every member no created child claimed (its own inliers and
+ *                the final left-overs) with their input flag bytes, and its
+ *                point, err and tinfo bit for bit.  So every member row of
+ *                the input is a member of exactly one output track.
+ * Outputs (device, buffers of their own: no output may overlap an input):
+ *   points [tmax_out][3], err [tmax_out], tinfo [tmax_out][4];
+ *   track_off [tmax_out + 1], track_rows [mmax], obs_inlier [mmax];
+ *   point_of_row [N]: the output id of the status-0 track in which the row is
+ *     a flagged member, else -1 (the input's point_of_row under the new
+ *     numbering, plus the child's id for each child inlier);
+ *   parent_of [tmax_out], generation [tmax_out]: the input track id, and 0 for
+ *     the parent itself, g for child g;
+ *   counts [8] = {T', members (counts_in[1]), tracks with status 0, the sum of
+ *     their n_inliers, children that did not fit in tmax_out, 0, children
+ *     created, parents with at least one created child}; the first four as
+ *     posfeat_triangulate lays them out.  Disjoint tracks of at least two
+ *     members give T' <= mmax / 2.
+ * Entries past T' / the member count are not written.
+ * Out of scope: a component larger than max_track is still dropped by
+ * posfeat_triangulate, and a status-1 parent is not tried again.
+ * Returns, before any device work: POSFEAT_E_INVALID for a null pointer (kp for
+ * N = 0 and cams, poses for nsets = 0 may be null), a bad set table, tmax or
+ * mmax negative, tmax + 1 or mmax above INT32_MAX, tmax_out below tmax or
+ * tmax_out + 1 above INT32_MAX, iters outside 8..1024, a non-finite or
+ * non-positive thr, min_angle_deg outside [0, 90), rounds outside 1..4, an
+ * output pointer equal to the input of the same name, ws not 256-B aligned, an
+ * fp64 buffer not 8-B aligned, an int32 buffer or kp not 4-B aligned;
+ * POSFEAT_E_WORKSPACE for ws_bytes below posfeat_split_tracks_workspace (0 for
+ * invalid arguments).
+ * Seven launches (and one copy of set_off) whatever T; stream-ordered, never
+ * synchronises the host; NOT graph-capturable (set_off is copied from pageable
+ * host memory).  No floating-point atomics.  Deterministic: the same inputs give
+ * the same bits, and what a parent becomes (its children, their points and
+ * members) depends only on its own members, their cameras, its input flags,
+ * iters, thr, min_angle_deg, seed and rounds (and, for the children that fit,
+ * on tmax_out). */
+size_t posfeat_split_tracks_workspace(const int32_t *set_off, int nsets, long long tmax,
+                                      long long mmax, long long tmax_out);
+int posfeat_split_tracks(const float *kp, const int32_t *set_off, int nsets, const double *cams,
+                         const double *poses, const double *points_in, const double *err_in,
+                         const int32_t *tinfo_in, const int32_t *track_off_in,
+                         const int32_t *track_rows_in, const uint8_t *inlier_in,
+                         const int32_t *counts_in, long long tmax, long long mmax, int iters,
+                         double thr, double min_angle_deg, uint64_t seed, int rounds,
+                         long long tmax_out, double *points, double *err, int32_t *tinfo,
+                         int32_t *track_off, int32_t *track_rows, uint8_t *obs_inlier,
+                         int32_t *point_of_row, int32_t *parent_of, int32_t *generation,
+                         int32_t *counts, void *ws, size_t ws_bytes, void *stream);
+
 /* Five-point RANSAC essential matrices and relative poses for every pair of a
  * list whose cameras are calibrated: the two-view problem between
  * posfeat_ransac_fundamental (no calibration) and posfeat_triangulate (known

@@ -262,6 +262,10 @@ SIGNATURES = {
                               [c_ll, c_ll, ctypes.c_double, ctypes.c_double, c_int, c_int] +
                               [c_void_p] * 8 + [c_size_t, c_void_p]),
     "posfeat_refine_point": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "posfeat_split_tracks_workspace": (c_size_t, [c_void_p, c_int, c_ll, c_ll, c_ll]),
+    "posfeat_split_tracks": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 9 +
+                             [c_ll, c_ll, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_uint64,
+                              c_int, c_ll] + [c_void_p] * 11 + [c_size_t, c_void_p]),
 }
 
 

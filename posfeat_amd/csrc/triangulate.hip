@@ -31,9 +31,13 @@
 // nothing depends on the order the slots were handed out.  Floating-point
 // contraction is off for the whole file: the hypothesis a lane scores and the
 // one the winner is rebuilt from are the same operations.
+//
+// posfeat_split_tracks (further down, with its own launch list) runs the same
+// device functions on the members a track's RANSAC left out.
 #include <math.h>
 
 #include "common.h"
+#include "split_plan.h"
 #include "triangulate_solve.h"
 
 #pragma clang fp contract(off)
@@ -498,6 +502,490 @@ unsigned grid_for(long long items, int per_block, unsigned cap) {
   return (unsigned)(g > (long long)cap ? cap : g);
 }
 
+// ---- posfeat_split_tracks: sequential RANSAC over a track's left-over members ----
+//
+// Seven launches whatever the number of parents:
+//
+//   split_init_kernel        per row: its set, its undistorted point,
+//                            point_of_row -1; marks, child counts, counts 0.
+//   split_lane_kernel        per parent: |L1| (-1 for a carried parent); parents
+//                            whose L1 has at most LANE_TRACK rows, one per lane:
+//                            the list in the workspace (the parent's own range),
+//                            the members' positions packed in one 64-bit word.
+//   split_wave_kernel        parents with a longer L1, one per wave, the list
+//                            and the positions in LDS; L_{g+1} is compacted from
+//                            L_g by ballot and prefix count, in member order.
+//   split_scan_sum / _top / _apply   the exclusive scan of (1 + children) over
+//                            the parents; the apply launch numbers the output
+//                            tracks (split_plan.h) and writes what is per track.
+//   split_emit_kernel        per parent: its range of track_rows dealt out to
+//                            the parent and its children, in member order.
+//
+// The generation loop runs inside the two track kernels, on the device
+// functions the triangulate kernels run, behind a test of the member row.
+
+struct SplitIn {
+  const double* points;
+  const double* err;
+  const int32_t* tinfo;
+  const int32_t* track_off;
+  const int32_t* track_rows;
+  const uint8_t* flags;
+  const int32_t* counts;
+  long long n, mmax;
+  int tmax, tmax_out, rounds;
+};
+
+struct SplitWs {
+  int32_t* list;
+  uint8_t* mark;
+  int32_t* nleft;
+  int32_t* nchild;
+  int32_t* ids;
+  int32_t* ncreated;
+  double* cpoint;
+  double* cerr;
+  int32_t* cinfo;
+  unsigned long long* bsum;
+};
+
+struct SplitOut {
+  double* points;
+  double* err;
+  int32_t* tinfo;
+  int32_t* track_off;
+  int32_t* track_rows;
+  uint8_t* obs_inlier;
+  int32_t* point_of_row;
+  int32_t* parent_of;
+  int32_t* generation;
+  int32_t* counts;
+};
+
+__device__ __forceinline__ int split_tracks_of(const SplitIn& in) {
+  const int T = in.counts[0];
+  return T < 0 ? 0 : (T > in.tmax ? in.tmax : T);
+}
+
+// posfeat_refine_points' rule: inside the member buffers, at most MAX_TRACK
+__device__ __forceinline__ bool split_range_ok(const SplitIn& in, int off, int m) {
+  return off >= 0 && m >= 0 && (long long)off + m <= in.mmax && m <= MAX_TRACK;
+}
+
+__device__ __forceinline__ bool split_row_valid(const SplitIn& in, int row) {
+  return row >= 0 && row < in.n;
+}
+
+__global__ __launch_bounds__(256) void split_init_kernel(
+    const float* __restrict__ kp, const int32_t* __restrict__ set_tab, int nsets,
+    const double* __restrict__ cams, SplitIn in, int32_t* __restrict__ setid,
+    double* __restrict__ und, SplitWs w, int32_t* __restrict__ point_of_row,
+    int32_t* __restrict__ counts) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r < 8) counts[r] = 0;
+  if (r < in.tmax) w.nchild[r] = 0, w.nleft[r] = -1;
+  if (r < in.mmax) w.mark[r] = 0;
+  if (r >= in.n) return;
+  int lo = 0, hi = nsets;  // invariant: set_tab[lo] <= r < set_tab[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (set_tab[mid] <= r) lo = mid; else hi = mid;
+  }
+  setid[r] = lo;
+  point_of_row[r] = -1;
+  double xu, yu;
+  undistort(cams + 8 * (long long)lo, (double)kp[2 * r], (double)kp[2 * r + 1], xu, yu);
+  und[2 * r] = xu, und[2 * r + 1] = yu;
+}
+
+// hypothesis(), a pair with a row outside the pool rejected before it is read
+__device__ __forceinline__ bool split_hypothesis(const Scene& sc, const SplitIn& in,
+                                                 const int32_t* rows, int m, int h, double (&X)[3],
+                                                 int& ri, int& rj) {
+  int i, j;
+  hyp_pair(sc.seed, rows[0], h, m, sc.iters, i, j);
+  ri = rows[i], rj = rows[j];
+  X[0] = X[1] = X[2] = 0.0;
+  if (!split_row_valid(in, ri) || !split_row_valid(in, rj)) return false;
+  double nm[4][4];
+  dlt_zero(nm);
+  row_dlt_add(sc, ri, nm);
+  row_dlt_add(sc, rj, nm);
+  return dlt_solve(nm, X) && pair_ok(sc, ri, rj, X);
+}
+
+__device__ __forceinline__ bool split_row_inlier(const Scene& sc, const SplitIn& in, int row,
+                                                 const double (&X)[3]) {
+  return split_row_valid(in, row) && row_inlier(sc, row, X);
+}
+
+__device__ __forceinline__ void split_store_child(const SplitWs& w, int t, int g,
+                                                  const double (&X)[3], double err, int nin,
+                                                  int best_h, int kept) {
+  const long long c = 4 * (long long)t + (g - 1);
+  w.cpoint[3 * c] = X[0], w.cpoint[3 * c + 1] = X[1], w.cpoint[3 * c + 2] = X[2];
+  w.cerr[c] = err;
+  int32_t* q = w.cinfo + 4 * c;
+  q[0] = 0, q[1] = nin, q[2] = best_h, q[3] = kept;
+}
+
+// |L1| of every parent that may split; the generations of those a lane can hold
+__global__ __launch_bounds__(64) void split_lane_kernel(Scene sc, SplitIn in, SplitWs w) {
+  const int T = split_tracks_of(in);
+  const int stride = gridDim.x * 64;
+  for (int t = blockIdx.x * 64 + threadIdx.x; t < T; t += stride) {
+    const int off = in.track_off[t], m = in.track_off[t + 1] - off;
+    if (!split_range_ok(in, off, m) || in.tinfo[4 * (long long)t] != 0) continue;
+    int len = 0;
+    for (int k = 0; k < m; ++k) len += in.flags[off + k] == 0 ? 1 : 0;
+    if (len < 2) continue;
+    w.nleft[t] = len;
+    if (len > LANE_TRACK) continue;
+    int32_t* rows = w.list + off;  // len <= m entries of the parent's own range
+    unsigned long long pos = 0ull;  // ten bits per entry: its member number
+    {
+      int a = 0;
+      for (int k = 0; k < m; ++k)
+        if (in.flags[off + k] == 0) {
+          rows[a] = in.track_rows[off + k];
+          pos |= (unsigned long long)k << (10 * a);
+          ++a;
+        }
+    }
+    int c = 0;
+    for (int g = 1; g <= in.rounds && len >= 2; ++g) {
+      const int H = num_hyp(len, sc.iters);
+      unsigned long long best = 0ull;
+      for (int h = 0; h < H; ++h) {
+        double X[3];
+        int ri, rj;
+        if (!split_hypothesis(sc, in, rows, len, h, X, ri, rj)) continue;
+        int cnt = 0;
+        for (int k = 0; k < len; ++k) cnt += split_row_inlier(sc, in, rows[k], X) ? 1 : 0;
+        const unsigned long long key = hyp_key(cnt, h);
+        best = key > best ? key : best;
+      }
+      if (best == 0ull) break;
+      const int h0 = (int)(0xffffffffu - (unsigned)best), c0 = (int)(best >> 32) - 1;
+      double X[3];
+      int ri, rj;
+      split_hypothesis(sc, in, rows, len, h0, X, ri, rj);
+      double nm[4][4], X1[3] = {0.0, 0.0, 0.0};
+      dlt_zero(nm);
+      for (int k = 0; k < len; ++k)
+        if (split_row_inlier(sc, in, rows[k], X)) row_dlt_add(sc, rows[k], nm);
+      bool keep = dlt_solve(nm, X1);
+      if (keep) {
+        int c1 = 0;
+        for (int k = 0; k < len; ++k) c1 += split_row_inlier(sc, in, rows[k], X1) ? 1 : 0;
+        keep = c1 >= c0 && pair_ok(sc, ri, rj, X1);
+      }
+      if (keep) X[0] = X1[0], X[1] = X1[1], X[2] = X1[2];
+      double sum = 0.0;
+      int nin = 0;
+      unsigned mask = 0u;
+      for (int k = 0; k < len; ++k) {
+        if (!split_row_valid(in, rows[k])) continue;
+        double z;
+        const double e2 = row_reproj2(sc, rows[k], X, z);
+        if (inlier_of(e2, z, sc.thr2)) {
+          sum = sum + sqrt(e2);
+          ++nin;
+          mask |= 1u << k;
+        }
+      }
+      if (nin < 2) break;
+      split_store_child(w, t, g, X, sum / (double)nin, nin, h0, keep ? 1 : 0);
+      int b = 0;
+      unsigned long long npos = 0ull;
+      for (int k = 0; k < len; ++k) {
+        const unsigned long long p = (pos >> (10 * k)) & 1023ull;
+        if ((mask >> k) & 1u) {
+          w.mark[off + (int)p] = (uint8_t)g;
+        } else {
+          rows[b] = rows[k];
+          npos |= p << (10 * b);
+          ++b;
+        }
+      }
+      pos = npos, len = b, c = g;
+    }
+    w.nchild[t] = c;
+  }
+}
+
+__device__ __forceinline__ int lanes_below(unsigned long long bal, int lane) {
+  return __popcll(bal & ((1ull << lane) - 1ull));
+}
+
+// one parent per wave (a workgroup is one wave): a hypothesis per lane, the
+// list in LDS.  A workgroup takes 64 consecutive parents at a time and works
+// through those whose L1 is longer than a lane holds; such a parent finishes
+// here however short its list becomes.
+__global__ __launch_bounds__(64) void split_wave_kernel(Scene sc, SplitIn in, SplitWs w) {
+  __shared__ int32_t srt[WAVE_LDS];    // the list, in member order
+  __shared__ uint16_t spos[WAVE_LDS];  // the member number of a list entry
+  __shared__ int32_t aux[WAVE_LDS];    // the inlier flags
+  __shared__ double ebuf[WAVE_LDS];    // the final reprojection errors
+  const int T = split_tracks_of(in), lane = threadIdx.x;
+  for (long long base = (long long)blockIdx.x * 64; base < T; base += (long long)gridDim.x * 64) {
+    const long long mine = base + lane;
+    unsigned long long todo = __ballot(mine < T && w.nleft[mine] > LANE_TRACK);
+    while (todo) {
+      const int t = (int)base + (__ffsll((long long)todo) - 1);
+      todo &= todo - 1;
+      const int off = in.track_off[t], m = in.track_off[t + 1] - off;  // the range is usable
+      __syncthreads();  // the parent before is done with the LDS
+      int len = 0;
+      for (int kb = 0; kb < m; kb += 64) {
+        const int k = kb + lane;
+        const bool left = k < m && in.flags[off + k] == 0;
+        const unsigned long long bal = __ballot(left);
+        if (left) {
+          const int d = len + lanes_below(bal, lane);
+          srt[d] = in.track_rows[off + k];
+          spos[d] = (uint16_t)k;
+        }
+        len += __popcll(bal);
+      }
+      __syncthreads();
+      int c = 0;
+      for (int g = 1; g <= in.rounds && len >= 2; ++g) {  // uniform: every exit is on wave-wide values
+        const int H = num_hyp(len, sc.iters);
+        unsigned long long best = 0ull;
+        for (int h = lane; h < H; h += 64) {
+          double X[3];
+          int ri, rj;
+          if (!split_hypothesis(sc, in, srt, len, h, X, ri, rj)) continue;
+          int cnt = 0;
+          for (int k = 0; k < len; ++k) cnt += split_row_inlier(sc, in, srt[k], X) ? 1 : 0;
+          const unsigned long long key = hyp_key(cnt, h);
+          best = key > best ? key : best;
+        }
+        best = wave_max(best);
+        if (best == 0ull) break;
+        const int h0 = (int)(0xffffffffu - (unsigned)best), c0 = (int)(best >> 32) - 1;
+        double X[3];
+        int ri, rj;
+        split_hypothesis(sc, in, srt, len, h0, X, ri, rj);  // every lane: the same bits
+        for (int k = lane; k < len; k += 64) aux[k] = split_row_inlier(sc, in, srt[k], X) ? 1 : 0;
+        __syncthreads();
+        double nm[4][4], X1[3] = {0.0, 0.0, 0.0};
+        dlt_zero(nm);
+        for (int k = 0; k < len; ++k)  // member order, every lane the same sum
+          if (aux[k]) row_dlt_add(sc, srt[k], nm);
+        bool keep = dlt_solve(nm, X1);
+        int c1 = 0;
+        for (int k = lane; k < len; k += 64) c1 += split_row_inlier(sc, in, srt[k], X1) ? 1 : 0;
+        c1 = wave_add(c1);
+        keep = keep && c1 >= c0 && pair_ok(sc, ri, rj, X1);
+        if (keep) X[0] = X1[0], X[1] = X1[1], X[2] = X1[2];
+        __syncthreads();
+        int nin = 0;
+        for (int k = lane; k < len; k += 64) {
+          bool inl = false;
+          double e2 = 0.0;
+          if (split_row_valid(in, srt[k])) {
+            double z;
+            e2 = row_reproj2(sc, srt[k], X, z);
+            inl = inlier_of(e2, z, sc.thr2);
+          }
+          aux[k] = inl ? 1 : 0;
+          ebuf[k] = inl ? sqrt(e2) : 0.0;
+          nin += inl ? 1 : 0;
+        }
+        nin = wave_add(nin);
+        __syncthreads();
+        if (nin < 2) break;
+        if (lane == 0) {
+          double sum = 0.0;
+          for (int k = 0; k < len; ++k)  // member order
+            if (aux[k]) sum = sum + ebuf[k];
+          split_store_child(w, t, g, X, sum / (double)nin, nin, h0, keep ? 1 : 0);
+        }
+        int kept = 0;
+        for (int kb = 0; kb < len; kb += 64) {
+          const int k = kb + lane;
+          const bool have = k < len;
+          const int row = have ? srt[k] : 0;
+          const uint16_t p = have ? spos[k] : (uint16_t)0;
+          const bool inl = have && aux[k] != 0;
+          if (inl) w.mark[off + p] = (uint8_t)g;
+          const bool left = have && !inl;
+          const unsigned long long bal = __ballot(left);
+          __syncthreads();  // the chunk is in registers before an entry of it is overwritten
+          if (left) {
+            const int d = kept + lanes_below(bal, lane);  // d <= k
+            srt[d] = row;
+            spos[d] = p;
+          }
+          kept += __popcll(bal);
+        }
+        __syncthreads();
+        len = kept, c = g;
+      }
+      if (lane == 0) w.nchild[t] = c;
+    }
+  }
+}
+
+constexpr int PARENTS_PER_THREAD = pfsplit::SCAN_PARENTS / 256;
+
+__device__ __forceinline__ unsigned long long split_scan_value(long long t, int T,
+                                                               const int32_t* __restrict__ nchild) {
+  return t < T ? 1ull + (unsigned long long)nchild[t] : 0ull;
+}
+
+__global__ __launch_bounds__(256) void split_scan_sum_kernel(SplitIn in, SplitWs w) {
+  __shared__ unsigned long long sh[256];
+  const int T = split_tracks_of(in);
+  const long long base =
+      (long long)blockIdx.x * pfsplit::SCAN_PARENTS + threadIdx.x * PARENTS_PER_THREAD;
+  unsigned long long v = 0;
+#pragma unroll
+  for (int k = 0; k < PARENTS_PER_THREAD; ++k) v += split_scan_value(base + k, T, w.nchild);
+  unsigned long long total;
+  block_exscan(v, sh, total);
+  if (threadIdx.x == 0) w.bsum[blockIdx.x] = total;
+}
+
+// one workgroup: bsum <- its exclusive scan; T', the counts that follow from
+// it, track_off[T']
+__global__ __launch_bounds__(256) void split_scan_top_kernel(long long nblk, SplitIn in, SplitWs w,
+                                                             SplitOut o) {
+  __shared__ unsigned long long sh[256];
+  unsigned long long carry = 0;
+  for (long long base = 0; base < nblk; base += 256) {
+    const long long i = base + threadIdx.x;
+    const unsigned long long v = i < nblk ? w.bsum[i] : 0ull;
+    unsigned long long total;
+    const unsigned long long ex = block_exscan(v, sh, total);
+    if (i < nblk) w.bsum[i] = carry + ex;
+    carry += total;
+  }
+  if (threadIdx.x == 0) {
+    const int T = split_tracks_of(in);
+    const long long all = (long long)carry;
+    const long long Tp = all < in.tmax_out ? all : in.tmax_out;  // T <= tmax <= tmax_out
+    o.counts[0] = (int32_t)Tp, o.counts[1] = in.counts[1];
+    o.counts[4] = (int32_t)(all - Tp), o.counts[6] = (int32_t)(Tp - T);
+    o.track_off[Tp] = in.track_off[T];
+  }
+}
+
+__global__ __launch_bounds__(256) void split_scan_apply_kernel(SplitIn in, SplitWs w, SplitOut o) {
+  __shared__ unsigned long long sh[256];
+  const int T = split_tracks_of(in);
+  const long long base =
+      (long long)blockIdx.x * pfsplit::SCAN_PARENTS + threadIdx.x * PARENTS_PER_THREAD;
+  unsigned long long val[PARENTS_PER_THREAD], v = 0;
+#pragma unroll
+  for (int k = 0; k < PARENTS_PER_THREAD; ++k) {
+    val[k] = split_scan_value(base + k, T, w.nchild);
+    v += val[k];
+  }
+  unsigned long long total;
+  unsigned long long at = block_exscan(v, sh, total) + w.bsum[blockIdx.x];
+  int npoints = 0, nobs = 0, nsplit = 0;
+#pragma unroll
+  for (int k = 0; k < PARENTS_PER_THREAD; ++k) {
+    const long long t = base + k;
+    if (t >= T) break;
+    const long long id = pfsplit::parent_id((long long)at, t, T, in.tmax_out);
+    const int cr = pfsplit::children_created((long long)at, (int)(val[k] - 1ull), t, T, in.tmax_out);
+    at += val[k];
+    w.ids[t] = (int32_t)id, w.ncreated[t] = cr;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o.points[3 * id + c] = in.points[3 * t + c];
+    o.err[id] = in.err[t];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o.tinfo[4 * id + c] = in.tinfo[4 * t + c];
+    o.track_off[id] = in.track_off[t];
+    o.parent_of[id] = (int32_t)t, o.generation[id] = 0;
+    if (in.tinfo[4 * t] == 0) ++npoints, nobs += in.tinfo[4 * t + 1];
+    for (int g = 1; g <= cr; ++g) {
+      const long long c = 4 * t + (g - 1), d = id + g;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) o.points[3 * d + i] = w.cpoint[3 * c + i];
+      o.err[d] = w.cerr[c];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) o.tinfo[4 * d + i] = w.cinfo[4 * c + i];
+      o.parent_of[d] = (int32_t)t, o.generation[d] = g;
+      ++npoints, nobs += w.cinfo[4 * c + 1];
+    }
+    nsplit += cr > 0 ? 1 : 0;
+  }
+  if (npoints) atomicAdd(o.counts + 2, npoints);
+  if (nobs) atomicAdd(o.counts + 3, nobs);
+  if (nsplit) atomicAdd(o.counts + 7, nsplit);
+}
+
+constexpr int EMIT_LANE = 8;  // members of a parent a lane deals out on its own
+
+__device__ __forceinline__ void split_emit(const SplitIn& in, const SplitOut& o, int dst, int row,
+                                           uint8_t flag, int g, int id, bool parent_ok) {
+  o.track_rows[dst] = row;
+  o.obs_inlier[dst] = g == 0 ? flag : (uint8_t)1;
+  if (!split_row_valid(in, row)) return;
+  if (g > 0) o.point_of_row[row] = id + g;
+  else if (flag != 0 && parent_ok) o.point_of_row[row] = id;
+}
+
+// the parent's range of track_rows: the members no created child claimed, then
+// child 1's, child 2's, ..., each in member order
+__global__ __launch_bounds__(64) void split_emit_kernel(SplitIn in, SplitWs w, SplitOut o) {
+  const int T = split_tracks_of(in), lane = threadIdx.x;
+  for (long long base = (long long)blockIdx.x * 64; base < T; base += (long long)gridDim.x * 64) {
+    const long long mine = base + lane;
+    bool wave_kind = false;
+    if (mine < T) {
+      const int t = (int)mine;
+      const int off = in.track_off[t], m = in.track_off[t + 1] - off;
+      const bool usable = split_range_ok(in, off, m);
+      wave_kind = usable && m > EMIT_LANE;
+      if (usable && m <= EMIT_LANE) {
+        const int id = w.ids[t], cr = w.ncreated[t];
+        const bool parent_ok = in.tinfo[4 * (long long)t] == 0;
+        int at = off;
+        for (int g = 0; g <= cr; ++g) {
+          if (g > 0) o.track_off[id + g] = at;
+          for (int k = 0; k < m; ++k) {
+            const int mk = w.mark[off + k];
+            if ((mk <= cr ? mk : 0) != g) continue;
+            split_emit(in, o, at, in.track_rows[off + k], in.flags[off + k], g, id, parent_ok);
+            ++at;
+          }
+        }
+      }
+    }
+    unsigned long long todo = __ballot(wave_kind);
+    while (todo) {
+      const int t = (int)base + (__ffsll((long long)todo) - 1);
+      todo &= todo - 1;
+      const int off = in.track_off[t], m = in.track_off[t + 1] - off;
+      const int id = w.ids[t], cr = w.ncreated[t];
+      const bool parent_ok = in.tinfo[4 * (long long)t] == 0;
+      int at = off;
+      for (int g = 0; g <= cr; ++g) {
+        if (g > 0 && lane == 0) o.track_off[id + g] = at;
+        for (int kb = 0; kb < m; kb += 64) {
+          const int k = kb + lane;
+          bool take = false;
+          if (k < m) {
+            const int mk = w.mark[off + k];
+            take = (mk <= cr ? mk : 0) == g;
+          }
+          const unsigned long long bal = __ballot(take);
+          if (take)
+            split_emit(in, o, at + lanes_below(bal, lane), in.track_rows[off + k], in.flags[off + k],
+                       g, id, parent_ok);
+          at += __popcll(bal);
+        }
+      }
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int posfeat_triangulate_dlt(const double* obs, int n, double* X) {
@@ -585,6 +1073,95 @@ extern "C" int posfeat_triangulate(const float* kp, const int32_t* set_off, int 
   // a workgroup per 64 consecutive tracks, which is how the kernel deals them
   hipLaunchKernelGGL(tri_wave_kernel, dim3(grid_for(L.tmax, 64, 1u << 16)), dim3(64), 0, st, sc,
                      track_off, track_rows, o);
+  PF_CHECK_LAUNCH();
+  return POSFEAT_OK;
+}
+
+extern "C" size_t posfeat_split_tracks_workspace(const int32_t* set_off, int nsets, long long tmax,
+                                                 long long mmax, long long tmax_out) {
+  pfsplit::Layout L;
+  if (pfsplit::layout(set_off, nsets, tmax, mmax, tmax_out, L) != 0) return 0;
+  return L.total;
+}
+
+extern "C" int posfeat_split_tracks(const float* kp, const int32_t* set_off, int nsets,
+                                    const double* cams, const double* poses, const double* points_in,
+                                    const double* err_in, const int32_t* tinfo_in,
+                                    const int32_t* track_off_in, const int32_t* track_rows_in,
+                                    const uint8_t* inlier_in, const int32_t* counts_in, long long tmax,
+                                    long long mmax, int iters, double thr, double min_angle_deg,
+                                    uint64_t seed, int rounds, long long tmax_out, double* points,
+                                    double* err, int32_t* tinfo, int32_t* track_off,
+                                    int32_t* track_rows, uint8_t* obs_inlier, int32_t* point_of_row,
+                                    int32_t* parent_of, int32_t* generation, int32_t* counts, void* ws,
+                                    size_t ws_bytes, void* stream) {
+  pfsplit::Layout L;
+  if (pfsplit::layout(set_off, nsets, tmax, mmax, tmax_out, L) != 0) return POSFEAT_E_INVALID;
+  if ((!kp && L.n > 0) || ((!cams || !poses) && nsets > 0) || !points_in || !err_in || !tinfo_in ||
+      !track_off_in || !track_rows_in || !inlier_in || !counts_in || !points || !err || !tinfo ||
+      !track_off || !track_rows || !obs_inlier || !point_of_row || !parent_of || !generation ||
+      !counts || !ws)
+    return POSFEAT_E_INVALID;
+  if (!pfsplit::params_ok(iters, thr, min_angle_deg, rounds)) return POSFEAT_E_INVALID;
+  // an output is a buffer of its own
+  if (points == points_in || err == err_in || tinfo == tinfo_in || track_off == track_off_in ||
+      track_rows == track_rows_in || obs_inlier == inlier_in || counts == counts_in)
+    return POSFEAT_E_INVALID;
+  const uintptr_t a8 = reinterpret_cast<uintptr_t>(points_in) | reinterpret_cast<uintptr_t>(err_in) |
+                       reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(err) |
+                       reinterpret_cast<uintptr_t>(cams) | reinterpret_cast<uintptr_t>(poses);
+  const uintptr_t a4 =
+      reinterpret_cast<uintptr_t>(tinfo_in) | reinterpret_cast<uintptr_t>(track_off_in) |
+      reinterpret_cast<uintptr_t>(track_rows_in) | reinterpret_cast<uintptr_t>(counts_in) |
+      reinterpret_cast<uintptr_t>(tinfo) | reinterpret_cast<uintptr_t>(track_off) |
+      reinterpret_cast<uintptr_t>(track_rows) | reinterpret_cast<uintptr_t>(point_of_row) |
+      reinterpret_cast<uintptr_t>(parent_of) | reinterpret_cast<uintptr_t>(generation) |
+      reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(kp);
+  if ((reinterpret_cast<uintptr_t>(ws) & 255) || (a8 & 7) || (a4 & 3)) return POSFEAT_E_INVALID;
+  if (ws_bytes < L.total) return POSFEAT_E_WORKSPACE;
+  hipStream_t st = pf_stream(stream);
+  char* w = static_cast<char*>(ws);
+  // the runtime has read a pageable source when the copy call returns (as
+  // posfeat_ransac_homography relies on)
+  if (hipMemcpyAsync(w + L.set_off, set_off, (size_t)(nsets + 1) * 4, hipMemcpyHostToDevice, st) !=
+      hipSuccess)
+    return POSFEAT_E_HIP;
+  const int32_t* set_tab = reinterpret_cast<const int32_t*>(w + L.set_off);
+  int32_t* setid = reinterpret_cast<int32_t*>(w + L.setid);
+  double* und = reinterpret_cast<double*>(w + L.und);
+  Scene sc{kp, setid, und, cams, poses, seed, iters, thr * thr,
+           cos(min_angle_deg * 3.14159265358979323846 / 180.0)};
+  SplitIn in{points_in, err_in, tinfo_in, track_off_in, track_rows_in, inlier_in, counts_in,
+             L.n,       mmax,   (int)tmax, (int)tmax_out, rounds};
+  SplitWs sw{reinterpret_cast<int32_t*>(w + L.list),     reinterpret_cast<uint8_t*>(w + L.mark),
+             reinterpret_cast<int32_t*>(w + L.nleft),    reinterpret_cast<int32_t*>(w + L.nchild),
+             reinterpret_cast<int32_t*>(w + L.ids),      reinterpret_cast<int32_t*>(w + L.ncreated),
+             reinterpret_cast<double*>(w + L.cpoint),    reinterpret_cast<double*>(w + L.cerr),
+             reinterpret_cast<int32_t*>(w + L.cinfo),
+             reinterpret_cast<unsigned long long*>(w + L.bsum)};
+  SplitOut o{points,     err,          tinfo,     track_off,  track_rows,
+             obs_inlier, point_of_row, parent_of, generation, counts};
+  long long items = L.n > tmax ? L.n : tmax;
+  items = items > mmax ? items : mmax;
+  items = items > 8 ? items : 8;
+  const unsigned scan_grid = grid_for(tmax, pfsplit::SCAN_PARENTS, 0x7fffffffu);
+  hipLaunchKernelGGL(split_init_kernel, dim3(grid_for(items, 256, 0x7fffffffu)), dim3(256), 0, st, kp,
+                     set_tab, nsets, cams, in, setid, und, sw, point_of_row, counts);
+  PF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(split_lane_kernel, dim3(grid_for(tmax, 64, 8192)), dim3(64), 0, st, sc, in, sw);
+  PF_CHECK_LAUNCH();
+  // a workgroup per 64 consecutive parents, which is how the kernel deals them
+  hipLaunchKernelGGL(split_wave_kernel, dim3(grid_for(tmax, 64, 1u << 16)), dim3(64), 0, st, sc, in,
+                     sw);
+  PF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(split_scan_sum_kernel, dim3(scan_grid), dim3(256), 0, st, in, sw);
+  PF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(split_scan_top_kernel, dim3(1), dim3(256), 0, st, L.nblk, in, sw, o);
+  PF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(split_scan_apply_kernel, dim3(scan_grid), dim3(256), 0, st, in, sw, o);
+  PF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(split_emit_kernel, dim3(grid_for(tmax, 64, 1u << 16)), dim3(64), 0, st, in, sw,
+                     o);
   PF_CHECK_LAUNCH();
   return POSFEAT_OK;
 }

@@ -5,7 +5,7 @@ without COLMAP.
 
   triangulate_pair_list(verified_npz, feature_dir, postfix, intrinsics, nvm,
                         thr=4.0, min_angle=1.5, iters=64, max_track=256, seed=0,
-                        refine=0) -> dict
+                        refine=0, split=0) -> dict
 
 ``verified_npz`` is what evaluation.verification.verify_pair_list wrote (pairs,
 match_offsets, matches); ``intrinsics`` and ``nvm`` are the two files the
@@ -15,7 +15,11 @@ MODEL w h params...``; the .nvm camera block: ``name f qw qx qy qz cx cy cz
 keypoint pool (a posed image without intrinsics raises); the verified matches
 of the pairs between them become edges (a match index outside its image's
 keypoints raises); pairs that name an image without a pose are skipped and
-counted.  geometry.triangulate_tracks runs once.  With ``refine`` = k > 0,
+counted.  geometry.triangulate_tracks runs once.  With ``split`` = k > 0,
+geometry.split_tracks (sequential RANSAC over each track's left-over members,
+rounds = k, the same iters, thr, min_angle and seed) runs on its result on the
+device, before any refinement: a track may become several, and every array
+below is the split result's.  With ``refine`` = k > 0,
 geometry.refine_tracks (points-only bundle adjustment, rounds = k, the same thr
 and min_angle) runs on its result on the device before the one read-back, and
 points, err, tinfo, obs_inlier, point_of_row and counts are the refined ones
@@ -35,7 +39,13 @@ points, err, tinfo, obs_inlier, point_of_row and counts are the refined ones
   with refine > 0 also:
   rinfo          [T, 4] (rounds used, taken steps, converged, flags changed)
   summary_unrefined   the summary of the triangulated points before refinement
-  counts_unrefined    posfeat_triangulate's counts
+  counts_unrefined    posfeat_triangulate's counts (posfeat_split_tracks' with split > 0)
+  with split > 0 also:
+  parent_of, generation   [T] the track of the triangulate call a track comes
+                 from, and 0 for that track itself, g for its g-th child
+                 (without refine; the refined result keeps the split's order)
+  summary_unsplit     the summary of the triangulated points before the split
+  counts_unsplit      posfeat_triangulate's counts
 write_model / read_model: COLMAP's text model (cameras.txt, images.txt,
 points3D.txt).
 """
@@ -163,7 +173,7 @@ def pair_list_edges(pairs, match_offsets, matches, index, set_off):
 
 
 def triangulate_pair_list(verified_npz, feature_dir, postfix, intrinsics, nvm, thr=4.0,
-                          min_angle=1.5, iters=64, max_track=256, seed=0, refine=0):
+                          min_angle=1.5, iters=64, max_track=256, seed=0, refine=0, split=0):
     _lib.require_device()
     device = torch.device("cuda", torch.cuda.current_device())
     ver = np.load(verified_npz) if isinstance(verified_npz, (str, os.PathLike)) else verified_npz
@@ -186,10 +196,22 @@ def triangulate_pair_list(verified_npz, feature_dir, postfix, intrinsics, nvm, t
     res = geometry.triangulate_tracks(kp_d, set_off, cams_d, poses_d,
                                       torch.from_numpy(edges).to(device), iters=iters, thr=thr,
                                       min_angle=min_angle, max_track=max_track, seed=seed)
+    unsplit = None
+    if int(split) > 0:
+        unsplit = res
+        res = geometry.split_tracks(kp_d, set_off, cams_d, poses_d, res, iters=iters, thr=thr,
+                                    min_angle=min_angle, rounds=int(split), seed=seed)
     if int(refine) > 0:
         res = geometry.refine_tracks(kp_d, set_off, cams_d, poses_d, res, thr=thr,
                                      min_angle=min_angle, rounds=int(refine))
     res = res.host()
+    if unsplit is not None:
+        res.pop("counts_unsplit", None)
+        raw = geometry._read_back(dict(err=unsplit.err, tinfo=unsplit.tinfo, counts=unsplit.counts))
+        c0 = raw["counts"].view(np.int32).copy()
+        res.update(counts_unsplit=c0, summary_unsplit=summary(dict(
+            err=raw["err"].view(np.float64)[:int(c0[0])],
+            tinfo=raw["tinfo"].view(np.int32).reshape(-1, 4)[:int(c0[0])])))
     unrefined = res.pop("unrefined", None)
     if unrefined is not None:
         res.update(summary_unrefined=summary(unrefined), counts_unrefined=unrefined["counts"])

@@ -555,6 +555,112 @@ def refine_tracks(kp_pool, set_off, cams, poses, tracks, thr=4.0, min_angle=1.5,
     return out
 
 
+class SplitTrackResult(TrackResult):
+    """What one posfeat_split_tracks call left on the device: a TrackResult of
+    its own buffers (capacity Tmax' = Mmax // 2 tracks) in which a track of the
+    input may have become several, plus ``parent_of`` [Tmax'] int32 (the input
+    track id) and ``generation`` [Tmax'] int32 (0 for the parent itself, g for
+    its g-th child).  ``counts`` = (T', members, status-0 points, inlier
+    observations, children that did not fit, 0, children created, parents that
+    split)."""
+
+    FIELDS = TrackResult.FIELDS + ("parent_of", "generation")
+    source = None        # the TrackResult that was split (split_tracks sets it)
+
+    def host(self):
+        """TrackResult.host() plus ``parent_of`` and ``generation`` and, where the
+        split TrackResult is attached, ``counts_unsplit``: one pinned copy, one
+        synchronisation."""
+        parts = {k: getattr(self, k) for k in self.FIELDS}
+        if self.source is not None:
+            parts.update(counts0=self.source.counts)
+        raw = _read_back(parts)
+        counts = raw["counts"].view(np.int32).copy()
+        T, M = int(counts[0]), int(counts[1])
+        out = dict(
+            points=raw["points"].view(np.float64).reshape(-1, 3)[:T].copy(),
+            err=raw["err"].view(np.float64)[:T].copy(),
+            tinfo=raw["tinfo"].view(np.int32).reshape(-1, 4)[:T].copy(),
+            track_off=raw["track_off"].view(np.int32)[:T + 1].copy(),
+            track_rows=raw["track_rows"].view(np.int32)[:M].copy(),
+            obs_inlier=raw["obs_inlier"][:M].copy(),
+            point_of_row=raw["point_of_row"].view(np.int32)[:self.point_of_row.shape[0]].copy(),
+            counts=counts,
+            parent_of=raw["parent_of"].view(np.int32)[:T].copy(),
+            generation=raw["generation"].view(np.int32)[:T].copy())
+        if self.source is not None:
+            out["counts_unsplit"] = raw["counts0"].view(np.int32).copy()
+        return out
+
+
+def split_tracks(kp_pool, set_off, cams, poses, tracks, iters=64, thr=4.0, min_angle=1.5, rounds=2,
+                 seed=0, tmax_out=None):
+    """posfeat_split_tracks on what ``tracks`` (a TrackResult of
+    triangulate_tracks on the same kp_pool, set_off, cams and poses) holds on the
+    device: sequential RANSAC, ``rounds`` in 1..4 generations, over the members
+    each track's own RANSAC left out.  iters, thr, min_angle and seed as in
+    triangulate_tracks.  ``tmax_out`` (default Mmax // 2, which disjoint tracks
+    of two members cannot exceed, and never below the input's capacity) is the
+    track capacity of the result.  The result can be passed to refine_tracks
+    and pose_correspondences as it is."""
+    _lib.require_device(kp_pool)
+    dev = kp_pool.device
+    set_off = np.ascontiguousarray(set_off, dtype=np.int32)
+    nsets = set_off.shape[0] - 1
+    if kp_pool.dtype != torch.float32 or kp_pool.dim() != 2 or kp_pool.shape[1] != 2:
+        raise ValueError("kp_pool must be a [N, 2] float32 tensor")
+    if nsets < 0 or kp_pool.shape[0] != int(set_off[-1]):
+        raise ValueError("kp_pool must have set_off[-1] rows")
+    poses = poses.reshape(-1, 12)
+    for name, t, shape, dt in (("cams", cams, (nsets, 8), torch.float64),
+                               ("poses", poses, (nsets, 12), torch.float64)):
+        if t.device != dev or t.dtype != dt or tuple(t.shape) != shape:
+            raise ValueError("%s must be a %s %s tensor on the keypoints' device" % (name, shape, dt))
+    N = int(set_off[-1])
+    tmax, mmax = int(tracks.track_off.shape[0]) - 1, int(tracks.track_rows.shape[0])
+    for name, dt, shape in (("points", torch.float64, (tracks.points.shape[0], 3)),
+                            ("err", torch.float64, (tracks.points.shape[0],)),
+                            ("tinfo", torch.int32, (tracks.points.shape[0], 4)),
+                            ("track_off", torch.int32, (tmax + 1,)),
+                            ("track_rows", torch.int32, (mmax,)),
+                            ("obs_inlier", torch.uint8, (mmax,)), ("counts", torch.int32, (8,))):
+        t = getattr(tracks, name)
+        if t.device != dev or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError("tracks.%s must be a contiguous %s %s tensor on the keypoints' device"
+                             % (name, shape, dt))
+    if tmax < 0 or tracks.points.shape[0] < max(tmax, 1) or tuple(tracks.point_of_row.shape) != (N,):
+        raise ValueError("tracks does not belong to this keypoint pool")
+    tout = max(tmax, mmax // 2) if tmax_out is None else int(tmax_out)
+    kp_pool, cams, poses = (t.contiguous() for t in (kp_pool, cams, poses))
+    so = ctypes.c_void_p(set_off.ctypes.data)
+    need = lib().posfeat_split_tracks_workspace(so, nsets, tmax, mmax, tout)
+    if need == 0:
+        raise ValueError("invalid set table, or tmax_out below the input's track capacity")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    out = SplitTrackResult(
+        points=torch.empty(max(tout, 1), 3, dtype=torch.float64, device=dev),
+        err=torch.empty(max(tout, 1), dtype=torch.float64, device=dev),
+        tinfo=torch.empty(max(tout, 1), 4, dtype=torch.int32, device=dev),
+        track_off=torch.empty(tout + 1, dtype=torch.int32, device=dev),
+        track_rows=torch.empty(max(mmax, 1), dtype=torch.int32, device=dev),
+        obs_inlier=torch.empty(max(mmax, 1), dtype=torch.uint8, device=dev),
+        point_of_row=torch.empty(max(N, 1), dtype=torch.int32, device=dev),
+        counts=torch.empty(8, dtype=torch.int32, device=dev),
+        parent_of=torch.empty(max(tout, 1), dtype=torch.int32, device=dev),
+        generation=torch.empty(max(tout, 1), dtype=torch.int32, device=dev))
+    check(lib().posfeat_split_tracks(
+        ptr(kp_pool), so, nsets, ptr(cams), ptr(poses), ptr(tracks.points), ptr(tracks.err),
+        ptr(tracks.tinfo), ptr(tracks.track_off), ptr(tracks.track_rows), ptr(tracks.obs_inlier),
+        ptr(tracks.counts), tmax, mmax, int(iters), float(thr), float(min_angle),
+        int(seed) & 0xFFFFFFFFFFFFFFFF, int(rounds), tout, ptr(out.points), ptr(out.err),
+        ptr(out.tinfo), ptr(out.track_off), ptr(out.track_rows), ptr(out.obs_inlier),
+        ptr(out.point_of_row), ptr(out.parent_of), ptr(out.generation), ptr(out.counts), ptr(ws),
+        need, stream_ptr(dev)))
+    out.point_of_row = out.point_of_row[:N]
+    out.source = tracks
+    return out
+
+
 def refine_point(obs, X0, steps=10):
     """posfeat_refine_point: obs [n >= 2, 22] rows (x, y, the 8 camera entries,
     the 12 entries of [R | t] row-major), X0 [3] -> (X [3], the cost sum |r|^2 at

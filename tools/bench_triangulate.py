@@ -50,8 +50,9 @@ def cameras(n):
     return cams, poses
 
 
-def scene(ncam, fill, rs):
-    """(kp [N, 2] fp32, set_off, cams, poses, edges [E, 2] int32, number of planted tracks)"""
+def scene(ncam, fill, rs, planting=None):
+    """(kp [N, 2] fp32, set_off, cams, poses, edges [E, 2] int32, number of planted tracks);
+    a dict ``planting`` gets 'track_of_row' [N]: the planted track of a row, -1 for none"""
     cams, poses = cameras(ncam)
     N = ncam * NKP
     kp = np.stack([rs.uniform(0, 640, N), rs.uniform(0, 480, N)], 1)
@@ -102,6 +103,9 @@ def scene(ncam, fill, rs):
     edges[flip] = edges[flip][:, ::-1]
     edges = edges[rs.permutation(len(edges))]
     set_off = (np.arange(ncam + 1) * NKP).astype(np.int32)
+    if planting is not None:
+        planting["track_of_row"] = np.full(N, -1, np.int64)
+        planting["track_of_row"][row[row >= 0]] = tid[row >= 0]
     return kp.astype(np.float32), set_off, cams, poses, edges.astype(np.int32), T
 
 
